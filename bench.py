@@ -18,6 +18,12 @@ to rank 0 over xGMI (--gather, the single-server fan-out topology).
 `value` is the whole-job aggregate encoded fps; the JSON also reports the p50/p99
 capture-to-packet encode latency (the server-side share of glass-to-glass) and
 how many concurrent 60 fps sessions that throughput sustains.
+
+A plain run sets up, warms up, times --steps steps and prints the result line.
+Everything else the benchmark measures (the end-to-end session checks with real
+servers and clients, the 4K / 8K HEVC and AV1 sessions, the CPU 480p session)
+runs only with --full. --dump-outputs DIR writes the packets of the last timed
+step as .npy arrays, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -60,13 +66,22 @@ def parse():
     p.add_argument("--backend", default="hip", choices=["hip", "cpu"])
     p.add_argument("--encoder", default="h264", choices=["h264", "jpeg", "hevc", "av1"],
                    help="h264 (headline, x264enc-striped equivalent), jpeg stripes, hevc or av1 full frames")
+    p.add_argument("--full", action="store_true",
+                   help="also run what a plain run leaves out: the end-to-end session checks (--e2e-*) before the "
+                        "timed window and the 4K / 8K / CPU 480p sessions (--extra-*) after it; without --full "
+                        "those options have no effect and their keys in the result line are null or absent")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the packets of the last timed step (what the path's caller "
+                        "receives) to DIR/packets.npy (every packet's bytes, concatenated, as float32) and "
+                        "DIR/packet_index.npy (one float64 row per packet: session, y, height, type, size); the "
+                        "inputs are the same from run to run")
     p.add_argument("--extra-4k", type=int, default=1,
-                   help="after the timed window: one 3840x2160 HEVC session (BASELINE config 3, 60 fps) and one "
+                   help="with --full, after the timed window: one 3840x2160 HEVC session (BASELINE config 3, 60 fps) and one "
                         "3840x2160 AV1 session (config 5, 120 fps), each timed over --extra-steps frames and "
                         "reported as extra keys (0 = skip)")
     p.add_argument("--extra-steps", type=int, default=60)
     p.add_argument("--extra-8k", type=int, default=1,
-                   help="after the 4K extras: one 7680x4320 HEVC session at 60 fps (CRF 25 and CBR 40 Mbit/s) and "
+                   help="with --full, after the 4K extras: one 7680x4320 HEVC session at 60 fps (CRF 25 and CBR 40 Mbit/s) and "
                         "one 7680x4320 AV1 session at 60 fps (the reference's largest display, selkies.py:266) on ONE "
                         "GPU, --extra-steps / 2 frames each (0 = skip)")
     p.add_argument("--jpeg-quality", type=int, default=40)
@@ -88,7 +103,7 @@ def parse():
                         "(parallel/dist_banded.py): rank 0 scatters the bands over RCCL, every rank encodes its "
                         "band on its GPU, packets are gathered to rank 0 each step; strong scaling")
     p.add_argument("--e2e-sessions", default="auto",
-                   help="before the timed window (single process, HIP, H.264 only): serve N 1080p60 sessions from "
+                   help="with --full, before the timed window (single process, HIP, H.264 only): serve N 1080p60 sessions from "
                         "real server processes (session hosts) to headless websocket clients for --e2e-seconds and report the "
                         "measured capture->client latency; a comma list is tried in order and the first N at "
                         "which every session sustains 60 fps is reported (tools/bench_e2e.py); 'auto' descends "
@@ -113,22 +128,37 @@ def parse():
                         "grab -> upload -> launch with two frames in flight -> packets -> per-frame callback), "
                         "driven in step mode from a pinned frame pool; encoder: Python threads calling the "
                         "encoder API directly")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:   # a plain run: the timed window and nothing else
+        args.e2e_sessions, args.e2e_av1, args.extra_4k, args.extra_8k = "0", "none", 0, 0
+    return args
 
 
-def run_capture_path(args, pool, local_rank, fast_cpu=False):
+def run_capture_path(args, pool, local_rank, fast_cpu=False, last_packets=None, last_frame=0):
     """Times the production serving loop: S native capture sessions on this GPU.
 
     Each session is a pixelflux ScreenCapture whose frame source is the pinned
     pool (source 4) in step mode: sk_capture_run grants K frames, the native loop
     grabs, uploads, launches (two frames in flight) and collects packets exactly
-    as when serving a display; Python only waits.
+    as when serving a display; Python only waits. With `last_packets` (a list with
+    one slot per session, --dump-outputs) every session has a frame callback that
+    counts its frames and copies the packets of frame number `last_frame`.
     """
     import pixelflux
     S = args.sessions
     H, W = pool.array.shape[1], pool.array.shape[2]
     caps = []
     null_cb = ctypes.cast(None, pixelflux.FrameCallback)   # packets stay native: bytes counted in stats()
+
+    def recorder(i):
+        seen = [0]
+
+        def on_frame(res, n, user):
+            seen[0] += 1
+            if seen[0] == last_frame:
+                last_packets[i] = [(res[k].stripe_y_start, res[k].stripe_height, res[k].type,
+                                    ctypes.string_at(res[k].data, res[k].size)) for k in range(n)]
+        return pixelflux.FrameCallback(on_frame)
 
     for i in range(S):
         if args.encoder == "jpeg":
@@ -152,7 +182,7 @@ def run_capture_path(args, pool, local_rank, fast_cpu=False):
                                         h264_me_full=-1 if fast_cpu else 0, h264_subpel=-1 if fast_cpu else 0)
         cs.pool = pool.array.ctypes.data
         c = pixelflux.ScreenCapture()
-        c.start_frame_capture(cs, null_cb)
+        c.start_frame_capture(cs, null_cb if last_packets is None else recorder(i))
         caps.append(c)
 
     def run_all(count):
@@ -387,6 +417,26 @@ def rc_desc(args) -> str:
     return f"CBR {args.kbps} kbit/s" if args.rc == "cbr" else f"{args.rc.upper()} {args.qp}"
 
 
+DUMP_MAX_VALUES = 15 * 2 ** 20   # float32 values in packets.npy: 60 MiB, the index rides in the rest of 64 MB
+
+
+def dump_outputs(dirname, sessions, rank=0):
+    """--dump-outputs: the packets of the last timed step. `sessions` holds, per session,
+    the list of (y, height, type, bytes) the path's caller received for that step (type:
+    the stripe result's type on the capture path, the key flag on the encoder path).
+    packets.npy: all bytes in session and packet order as float32; beyond DUMP_MAX_VALUES
+    a fixed sample (positions drawn with seed 0, ascending). packet_index.npy: one float64
+    row (session, y, height, type, size) per packet. Ranks above 0 add _rank<N>."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = [(i, y, h, typ, len(data)) for i, pk in enumerate(sessions) for y, h, typ, data in pk or []]
+    blob = np.frombuffer(b"".join(data for pk in sessions for _, _, _, data in pk or []), dtype=np.uint8)
+    if blob.size > DUMP_MAX_VALUES:
+        blob = blob[np.sort(np.random.default_rng(0).integers(0, blob.size, DUMP_MAX_VALUES))]
+    suffix = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(dirname, f"packets{suffix}.npy"), blob.astype(np.float32))
+    np.save(os.path.join(dirname, f"packet_index{suffix}.npy"), np.asarray(rows, dtype=np.float64).reshape(-1, 5))
+
+
 def run_dist_bands(args, torch, dist, rank, world, local_rank):
     """One WxH session across all ranks; returns the result dict on rank 0."""
     from selkies_gstreamer_amd.parallel.dist_banded import DistBandedEncoder
@@ -426,6 +476,8 @@ def run_dist_bands(args, torch, dist, rank, world, local_rank):
     enc.close()
     if rank != 0:
         return None
+    if args.dump_outputs:   # rank 0 holds the whole frame's packets of the last step
+        dump_outputs(args.dump_outputs, [[(p.y, p.h, int(p.key), p.data) for p in pk]])
     fps = args.steps / elapsed
     lat_ms = np.asarray(lat) * 1e3
     return {
@@ -520,8 +572,11 @@ def main():
     for i in range(args.pool):
         src.frame(i, out=pool.array[i])
     caps = None
+    last_pk = [None] * S   # --dump-outputs: every session's packets of the last timed step
     if args.path == "capture":
-        caps, run_caps = run_capture_path(args, pool, local_rank)
+        caps, run_caps = run_capture_path(args, pool, local_rank,
+                                          last_packets=last_pk if args.dump_outputs else None,
+                                          last_frame=args.warmup + args.steps)
         encs = []
     elif args.encoder == "jpeg":
         encs = [JpegEncoder(W, H, stripe_height=args.stripe_height, quality=args.jpeg_quality, use_paint_over=False,
@@ -561,6 +616,7 @@ def main():
                 if record:
                     lat[i].append(time.perf_counter() - t_up.pop(t))
                     nbytes[i] += sum(len(p.data) for p in pk)
+                    last_pk[i] = pk
             return
         if args.overlap and hasattr(e, "upload"):
             t_up = time.perf_counter()
@@ -575,6 +631,7 @@ def main():
                 if record:
                     lat[i].append(time.perf_counter() - t_up)
                     nbytes[i] += sum(len(p.data) for p in pk)
+                    last_pk[i] = pk
                 if nxt:
                     e.launch()
                     t_up = t_next
@@ -585,6 +642,7 @@ def main():
             if record:
                 lat[i].append(time.perf_counter() - a)
                 nbytes[i] += sum(len(p.data) for p in pk)
+                last_pk[i] = pk
 
     gathered = [0]
 
@@ -603,6 +661,7 @@ def main():
                 step.extend((i, p.data) for p in pk)
                 if record:
                     nbytes[i] += sum(len(p.data) for p in pk)
+                    last_pk[i] = pk
             got = gather_packets(step) if dist is not None else [(0, i, d) for i, d in step]
             if record:
                 dt = time.perf_counter() - a
@@ -671,6 +730,10 @@ def main():
         total_bytes = float(stats[2])
         p50, p99, lat_max = float(stats[3]), float(stats[4]), float(stats[5])
     fps = frames / elapsed
+    if args.dump_outputs:
+        if caps is None:
+            last_pk = [[(p.y, p.h, int(p.key), p.data) for p in pk or []] for pk in last_pk]
+        dump_outputs(args.dump_outputs, last_pk, rank)
     for e in encs:
         e.close()
     encs = []

@@ -16,7 +16,7 @@ def test_bench_two_ranks_report_per_gpu_e2e(world, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(29500 + os.getpid() % 1000), "bench.py",
            "--gpus", str(world), "--backend", "cpu", "--path", "encoder", "--width", "256", "--height", "128",
-           "--sessions", "1", "--steps", "3", "--warmup", "1", "--extra-4k", "0",
+           "--sessions", "1", "--steps", "3", "--warmup", "1", "--full", "--extra-4k", "0",
            "--e2e-force", "--e2e-sessions", "2", "--e2e-seconds", "2", "--e2e-warmup", "2"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -43,7 +43,7 @@ def test_bench_world8_capture_path_cpu_quota(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(29700 + os.getpid() % 1000), "bench.py",
            "--gpus", str(world), "--backend", "cpu", "--width", "256", "--height", "128",
-           "--sessions", "1", "--steps", "3", "--warmup", "1", "--extra-4k", "0", "--e2e-force"]
+           "--sessions", "1", "--steps", "3", "--warmup", "1", "--full", "--extra-4k", "0", "--e2e-force"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]

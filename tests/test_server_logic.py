@@ -221,16 +221,16 @@ def test_gamepad_mapping():
     assert len(pack_input_events(e, 8)) == 48 and len(pack_input_events(e, 4)) == 32
 
 
-def test_gamepad_socket_roundtrip(tmp_path):
+def test_gamepad_socket_roundtrip(sock_dir):
     async def run():
-        hub = GamepadHub(str(tmp_path), slots=1)
+        hub = GamepadHub(str(sock_dir), slots=1)
         await hub.start()
-        r, w = await asyncio.open_unix_connection(str(tmp_path / "selkies_js0.sock"))
+        r, w = await asyncio.open_unix_connection(str(sock_dir / "selkies_js0.sock"))
         cfg = await r.readexactly(1360)
         assert cfg == pack_js_config()
         w.write(bytes([8]))
         await w.drain()
-        re_, we = await asyncio.open_unix_connection(str(tmp_path / "selkies_event1000.sock"))
+        re_, we = await asyncio.open_unix_connection(str(sock_dir / "selkies_event1000.sock"))
         await re_.readexactly(1360)
         we.write(bytes([8]))
         await we.drain()
@@ -290,9 +290,9 @@ def test_input_keys_and_mouse():
     assert ev[-4:] == [("key", 0x68, True), ("key", 0x68, False), ("key", 0x69, True), ("key", 0x69, False)]
 
 
-def test_input_gamepad_dispatch(tmp_path):
+def test_input_gamepad_dispatch(sock_dir):
     async def run():
-        hub = GamepadHub(str(tmp_path), slots=4)
+        hub = GamepadHub(str(sock_dir), slots=4)
         await hub.start()
         h = InputHandler(RecordingInjector(), gamepads=hub)
         await h.on_message("js,c,1," + base64.b64encode(b"Pad").decode() + ",4,17")

@@ -72,17 +72,17 @@ asyncio.run(main(sys.argv[1]))
 '''
 
 
-def test_js_interposer_end_to_end(shims, tmp_path):
+def test_js_interposer_end_to_end(shims, sock_dir):
     """Gamepad socket server and LD_PRELOADed client run as two real processes."""
     interposer, _ = shims
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    srv = subprocess.Popen([sys.executable, "-c", SERVER, str(tmp_path)], cwd=root, stdin=subprocess.PIPE,
+    srv = subprocess.Popen([sys.executable, "-c", SERVER, str(sock_dir)], cwd=root, stdin=subprocess.PIPE,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                            env=dict(os.environ, PYTHONPATH=root))
     p = None
     try:
         assert srv.stdout.readline().strip() == "ready", srv.stderr.read()
-        env = dict(os.environ, LD_PRELOAD=str(interposer), SELKIES_INTERPOSER_SOCKET_DIR=str(tmp_path))
+        env = dict(os.environ, LD_PRELOAD=str(interposer), SELKIES_INTERPOSER_SOCKET_DIR=str(sock_dir))
         p = subprocess.Popen([sys.executable, "-c", CHILD], env=env, stdout=subprocess.PIPE,
                              stderr=subprocess.PIPE, text=True)
         line = p.stdout.readline()
@@ -175,37 +175,44 @@ def test_fake_udev_enumeration(shims):
         assert ver in syms
 
 
-REF_UDEV_SYM = "/root/reference/addons/fake-udev/libudev.sym"
-
-
-def test_fake_udev_exports_every_reference_symbol(shims):
-    _, udev_path = shims
-    """Every symbol of the reference's version script (libudev.sym) is exported, with its
-    version node; a game linked against any of them resolves under the preload."""
-    import re
-    if not os.path.exists(REF_UDEV_SYM):
-        pytest.skip("reference tree not mounted")
-    want = {}
-    node = None
-    for line in open(REF_UDEV_SYM):
-        m = re.match(r"\s*(LIBUDEV_\d+)\s*\{", line)
-        if m:
-            node = m.group(1)
-            continue
-        m = re.match(r"\s*(udev_\w+)\s*;", line)
-        if m and node:
-            want[m.group(1)] = node
-    assert len(want) >= 90
-    out = subprocess.run(["objdump", "-T", str(udev_path)], capture_output=True, text=True).stdout
+def _udev_exports(path):
+    """{symbol: version node} of the udev_* functions a libudev exports (objdump -T)."""
+    out = subprocess.run(["objdump", "-T", str(path)], capture_output=True, text=True).stdout
     have = {}
     for line in out.splitlines():
         f = line.split()
         if len(f) >= 2 and f[-1].startswith("udev_"):
-            have[f[-1]] = f[-2]
+            have[f[-1]] = f[-2].strip("()")
+    return have
+
+
+def _system_libudev():
+    import sysconfig
+    dirs = [f"/lib/{sysconfig.get_config_var('MULTIARCH')}", f"/usr/lib/{sysconfig.get_config_var('MULTIARCH')}",
+            "/lib64", "/usr/lib64", "/lib", "/usr/lib"]
+    return next((os.path.join(d, "libudev.so.1") for d in dirs if os.path.exists(os.path.join(d, "libudev.so.1"))), None)
+
+
+def test_fake_udev_exports_every_reference_symbol(shims):
+    """Every symbol of libudev's version script (what the reference's fake-udev exports too)
+    is exported, with its version node; a game linked against any of them resolves under
+    the preload. The list is read from the system's own libudev.so.1, the library such a
+    game was linked against."""
+    _, udev_path = shims
+    real = _system_libudev()
+    if real is None:
+        pytest.skip("needs the system library libudev.so.1, found none")
+    want = _udev_exports(real)
+    assert len(want) >= 90
+    assert all(v.startswith("LIBUDEV_") for v in want.values()), want
+    have = _udev_exports(udev_path)
     missing = sorted(set(want) - set(have))
     assert not missing, missing
-    wrong = {k: (have[k], v) for k, v in want.items() if have[k].strip("()") != v}
+    wrong = {k: (have[k], v) for k, v in want.items() if have[k] != v}
     assert not wrong, wrong
+    # the enumerate extensions of test_fake_udev_children_devicenode_sysnum, in the newest node
+    for f in ("udev_enumerate_add_match_devicenode", "udev_enumerate_add_match_sysnum", "udev_enumerate_scan_children"):
+        assert have.get(f) == "LIBUDEV_247", (f, have.get(f))
 
 
 def test_fake_udev_children_devicenode_sysnum(shims):

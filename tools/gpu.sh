@@ -8,7 +8,7 @@
 #   py     TAG SCRIPT [ARGS...]  python SCRIPT ARGS > gpurun_out/TAG/out.txt
 #   profpy TAG SCRIPT [ARGS...]  rocprofv3 --kernel-trace --stats of python SCRIPT ARGS + kernel table
 #   rate   TAG [CODECS...]       K10 CBR traces (rc_trace.py) per codec + tools/rate_report.py
-#   driver TAG                   the driver's bench command (bench.py --gpus 1 --steps 20 --warmup 5)
+#   driver TAG                   the driver's bench command with every extra (bench.py --gpus 1 --steps 20 --warmup 5 --full)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 ROOT=$(pwd)
@@ -65,8 +65,8 @@ rate)
     python tools/rate_report.py "$OUT" > "$OUT/rate.md" && cat "$OUT/rate.md" | head -40
     exit 0 ;;
 driver)
-    # the driver's round-end command (bench.py --gpus 1 --steps 20 --warmup 5) + its kernel profile
-    timeout -k 10 500 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.jsonl" 2> "$OUT/bench.err"
+    # the driver's round-end command with the end-to-end checks and the 4K / 8K sessions (--full)
+    timeout -k 10 500 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.jsonl" 2> "$OUT/bench.err"
     rc=$?; tail -1 "$OUT/bench.jsonl" | cut -c1-1500; [ $rc -ne 0 ] && { tail -20 "$OUT/bench.err"; exit $rc; }
     exit 0 ;;
 pmcpy)
