@@ -1,5 +1,5 @@
 // Device buffers and launch interface of the HIP AV1 back end. It runs after the
-// H.264 front end (k_convert_damage, k_plan, k_me_mfma, k_motion_search, k_decide)
+// H.264 front end (k_convert_damage, k_plan, k_me, k_decide)
 // on the same FrameArgs and before k_commit (reference / motion-field update).
 #pragma once
 #include <hip/hip_runtime.h>

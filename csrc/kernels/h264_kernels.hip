@@ -8,14 +8,15 @@
 //
 // Stages (all bit-exact with the CPU reference csrc/codec/h264_cpu.cpp):
 //   k_convert_damage  K1+K3  BGRx -> NV12-planar YUV 4:2:0 + per-MB damage bits
-//   k_me_mfma         K4a    exhaustive +-16 search: int8 MFMA cross-correlation (SSD)
-//   k_motion_search   K4     candidate + diamond integer search, v_sad_u8
+//   k_me              K4a+K4 exhaustive +-16 search (int8 MFMA cross-correlation, SSD), then
+//                            candidate + diamond integer search (v_sad_u8) on the same LDS window
+//   k_motion_search   K4     the candidate + diamond search alone (me_full off)
 //   k_decide                 per-slice scene-cut decision
 //   k_code_inter      K6     MC, transform, quant/decimation, QP escalation, recon
 //   k_code_intra      K5+K6  Intra16x16 wavefront (one wave per MB row, lag 2)
 //   k_cavlc           K8     per-MB CAVLC: lanes code residual blocks in parallel,
 //                            bit offsets by wave prefix-sum, LDS atomicOr packing
-//   k_slice_scan, k_mb_concat, k_ep_*   K9  slice header + MB offsets, MB bit
+//   k_slice_scan, k_mb_concat, k_ep_count, k_ep_write   K9  slice header + MB offsets, MB bit
 //                            concatenation, tile-parallel emulation prevention
 //                            straight into host-mapped packet slots
 //   k_commit                 MV-field update (+ plain reference copy when K7 is off)
@@ -23,6 +24,7 @@
 #include "h264_gpu.h"
 #include "../codec/color.h"
 #include "../codec/h264_mb.h"
+#include "../codec/h264_ep.h"
 
 namespace sk {
 namespace h264 {
@@ -405,42 +407,54 @@ __device__ __forceinline__ uint32_t load_ref4(const uint8_t* row, int x, int str
     return v;
 }
 
-__device__ __forceinline__ int me_sad(const FrameArgs& a, const uint8_t* refy, uint32_t sw, int mbx,
-                                      int mby, int dx, int dy, int ylo, int yhi) {
+// This lane's 4-pixel share of a 16x16 SAD against global memory (lane: 4 samples of
+// row l / 4). A share is <= 1020, so two candidates pack into one 32-bit wave sum
+// (64 x 1020 < 65536).
+__device__ __forceinline__ uint32_t me_sad_lane(const FrameArgs& a, const uint8_t* refy, uint32_t sw, int mbx,
+                                                int mby, int dx, int dy, int ylo, int yhi) {
     int l = lane_id();
     int row = l >> 2, col4 = (l & 3) * 4;
     int sy = sk_clip(mby * 16 + row + dy, ylo, yhi);
     uint32_t rw = load_ref4(refy + (size_t)sy * a.stride_y, mbx * 16 + col4 + dx, a.stride_y);
-    return wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
-}
-
-// Reference window cached in LDS for the diamond refinement: +-kWin pixels
-// around the best predictor, 32 rows x 36 bytes (the extra word serves the
-// aligned-pair read of the last unaligned column). Window bytes are produced
-// by load_ref4, so every SAD is identical to the global-memory path.
-constexpr int kWin = 8;
-constexpr int kWinWords = 10;  // words per LDS row (40 B)
-
-// This lane's 4-pixel share of win_sad (<= 1020, so two candidates pack into one
-// 32-bit wave sum: 64 x 1020 < 65536).
-__device__ __forceinline__ uint32_t win_sad_lane(const uint32_t* win, uint32_t sw, int ox, int oy) {
-    const int l = lane_id();
-    const int row = l >> 2, col4 = (l & 3) * 4;
-    const int bc = col4 + ox + kWin;
-    const uint32_t* w = win + (row + oy + kWin) * kWinWords + (bc >> 2);
-    const int sh = bc & 3;
-    const uint32_t rw = sh ? __builtin_amdgcn_alignbyte(w[1], w[0], sh) : w[0];
     return __builtin_amdgcn_sad_u8(sw, rw, 0u);
 }
 
-__device__ __forceinline__ int win_sad(const uint32_t* win, uint32_t sw, int ox, int oy) {
+__device__ __forceinline__ int me_sad(const FrameArgs& a, const uint8_t* refy, uint32_t sw, int mbx,
+                                      int mby, int dx, int dy, int ylo, int yhi) {
+    return wave_sum((int)me_sad_lane(a, refy, sw, mbx, mby, dx, dy, ylo, yhi));
+}
+
+// Reference window of one macroblock cached in LDS: the 16x16 blocks at the vectors
+// (cx + ox, cy + oy), |ox|, |oy| <= rad, rows of `stride` words. Window bytes are
+// produced by load_ref4 with the row clamps of me_sad, so every SAD read from a
+// window is identical to the global-memory path. Two windows exist:
+//   small  +-kWin around the best predictor, 32 rows x 36 bytes in rows of kWinWords
+//          (the extra word serves the aligned-pair read of the last unaligned column)
+//   big    the +-kFsR window of the exhaustive search (k_me), centred on the zero
+//          vector, 48 rows x 48 bytes in rows of kFsWinWords
+constexpr int kWin = 8;
+constexpr int kWinWords = 10;               // words per LDS row (40 B)
+constexpr int kFsWinWords = kFsWin / 4 + 1; // big window: 12 words + 1 of padding (see k_me)
+
+struct MeWin {
+    const uint32_t* w;
+    int stride;    // words per row
+    int rad;       // < 0: no window yet
+    int cx, cy;    // vector of the window centre
+    __device__ __forceinline__ bool has(int dx, int dy) const {
+        return dx - cx >= -rad && dx - cx <= rad && dy - cy >= -rad && dy - cy <= rad;
+    }
+};
+
+// This lane's share of the SAD at vector (dx, dy) from the window (has(dx, dy) holds).
+__device__ __forceinline__ uint32_t win_sad_lane(const MeWin& wn, uint32_t sw, int dx, int dy) {
     const int l = lane_id();
     const int row = l >> 2, col4 = (l & 3) * 4;
-    const int bc = col4 + ox + kWin;              // byte column inside the window row
-    const uint32_t* w = win + (row + oy + kWin) * kWinWords + (bc >> 2);
+    const int bc = col4 + dx - wn.cx + wn.rad;     // byte column inside the window row
+    const uint32_t* w = wn.w + (row + dy - wn.cy + wn.rad) * wn.stride + (bc >> 2);
     const int sh = bc & 3;
     const uint32_t rw = sh ? __builtin_amdgcn_alignbyte(w[1], w[0], sh) : w[0];
-    return wave_sum((int)__builtin_amdgcn_sad_u8(sw, rw, 0u));
+    return __builtin_amdgcn_sad_u8(sw, rw, 0u);
 }
 
 // sum |Y - mean| of a 16x16 MB, one wave (lane: 4 samples of row l / 4)
@@ -453,104 +467,105 @@ __device__ __forceinline__ int mb_activity(uint32_t sw) {
     return wave_sum(dev);
 }
 
-__global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
-    __shared__ uint32_t win[32 * kWinWords];
-    int nmb = a.mb_w * a.mb_h;
-    int idx = xcd_remap(blockIdx.x, gridDim.x);
-    if (idx >= nmb) return;
-    int mbx = idx % a.mb_w, mby = idx / a.mb_w;
-    int s = mby / a.rows_per_slice;
-    const SliceTask t = a.tasks[s];
-    if (t.action != ACT_P && t.action != ACT_I) return;
-    int l = lane_id();
-    int row = l >> 2, col4 = (l & 3) * 4;
-    uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + row) * a.stride_y +
-                                                     mbx * 16 + col4);
+// K4 search of one macroblock of an ACT_P / ACT_I slice by one wave: predictors in the
+// order of the CPU reference, diamond refinement, activity, second-reference test and
+// the MeResult store. sw: this lane's source word; (fsx, fsy): the exhaustive-search
+// winner, a predictor when have_fs. `win` is the wave's LDS region (at least 32 rows
+// of kWinWords): with `big` it holds the filled +-kFsR window and SADs at vectors
+// inside it are read from there; other vectors (me_range reaches further) come from
+// global memory. Without it, or when the best predictor lies outside it, the small
+// window is filled around the best predictor for the diamond.
+__device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask& t, int idx, int mbx, int mby,
+                                             uint32_t sw, bool have_fs, int fsx, int fsy, uint32_t* win, bool big) {
+    const int l = lane_id();
     if (t.action == ACT_I) {   // planned key frame: only the activity (K10's intra complexity)
         const int dev = mb_activity(sw);
         if (l == 0) a.me[idx] = MeResult{0, 0, 0, dev, 0, 0, 0};
         return;
     }
-    int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
+    const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
     const int lam = lambda_for_qp(rc_me_qp(*a.rc, t.qp));
     const int R = a.me_range;
-    // candidates (same order as the CPU reference)
-    int cx[7], cy[7], n = 0;
-    cx[0] = 0; cy[0] = 0; n = 1;
-    auto add = [&](int ox, int oy) {
-        int j = oy * a.mb_w + ox;
-        cx[n] = sk_clip(a.mvfield[2 * j], -R, R);
-        cy[n] = sk_clip(a.mvfield[2 * j + 1], -R, R);
-        n++;
+    MeWin wn{win, big ? kFsWinWords : kWinWords, big ? kFsR : -1, 0, 0};
+    auto sad_lane = [&](int dx, int dy) {
+        return wn.has(dx, dy) ? win_sad_lane(wn, sw, dx, dy) : me_sad_lane(a, a.ref.y, sw, mbx, mby, dx, dy, ylo, yhi);
     };
-    add(mbx, mby);
-    if (mbx > 0) add(mbx - 1, mby);
-    if (mbx + 1 < a.mb_w) add(mbx + 1, mby);
-    if (mby - 1 >= t.pic_row0) add(mbx, mby - 1);
-    if (mby + 1 < t.pic_row0 + t.pic_rows) add(mbx, mby + 1);
-    if (a.me_full && a.mb_dirty[idx]) {   // K4a winner (k_me_mfma)
-        cx[n] = sk_clip(a.fs_mv[2 * idx], -R, R);
-        cy[n] = sk_clip(a.fs_mv[2 * idx + 1], -R, R);
-        n++;
+    // candidates (same order as the CPU reference): zero, the MB's own previous vector,
+    // left, right, up, down, the exhaustive-search winner; a slot that does not exist
+    // is skipped
+    int cx[7], cy[7];
+    bool ok[7];
+    auto slot = [&](int k, bool valid, int ox, int oy) {
+        const int j = valid ? oy * a.mb_w + ox : idx;
+        ok[k] = valid;
+        cx[k] = sk_clip(a.mvfield[2 * j], -R, R);
+        cy[k] = sk_clip(a.mvfield[2 * j + 1], -R, R);
+    };
+    cx[0] = 0; cy[0] = 0; ok[0] = true;
+    slot(1, true, mbx, mby);
+    slot(2, mbx > 0, mbx - 1, mby);
+    slot(3, mbx + 1 < a.mb_w, mbx + 1, mby);
+    slot(4, mby - 1 >= t.pic_row0, mbx, mby - 1);
+    slot(5, mby + 1 < t.pic_row0 + t.pic_rows, mbx, mby + 1);
+    ok[6] = have_fs;   // K4a winner
+    cx[6] = sk_clip(fsx, -R, R);
+    cy[6] = sk_clip(fsy, -R, R);
+    int sd[8];
+    {   // every candidate's lane share first (independent loads), two per wave sum
+        uint32_t p[8];
+#pragma unroll
+        for (int k = 0; k < 7; k++) p[k] = ok[k] ? sad_lane(cx[k], cy[k]) : 0u;
+        p[7] = 0u;
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) {
+            const uint32_t s2 = (uint32_t)wave_sum((int)(p[k] | (p[k + 1] << 16)));
+            sd[k] = (int)(s2 & 0xffff);
+            sd[k + 1] = (int)(s2 >> 16);
+        }
     }
     int bx = 0, by = 0;
-    int bsad = me_sad(a, a.ref.y, sw, mbx, mby, 0, 0, ylo, yhi);
+    int bsad = sd[0];
     int bcost = bsad + lam * (sk_se_bits(0) + sk_se_bits(0));
-    for (int i = 1; i < n; i++) {
-        int sd = me_sad(a, a.ref.y, sw, mbx, mby, cx[i], cy[i], ylo, yhi);
-        int c = sd + lam * (sk_se_bits(4 * cx[i]) + sk_se_bits(4 * cy[i]));
-        if (c < bcost) { bcost = c; bx = cx[i]; by = cy[i]; bsad = sd; }
+#pragma unroll
+    for (int k = 1; k < 7; k++) {
+        if (!ok[k]) continue;
+        int c = sd[k] + lam * (sk_se_bits(4 * cx[k]) + sk_se_bits(4 * cy[k]));
+        if (c < bcost) { bcost = c; bx = cx[k]; by = cy[k]; bsad = sd[k]; }
     }
-    // fill the LDS window around the best predictor: lane -> (row l>>1, 5 words)
-    const int cx0 = bx, cy0 = by;
-    {
+    if (!(big && wn.has(bx, by))) {
+        // fill the small window around the best predictor: lane -> (row l>>1, 5 words)
+        wave_sync();   // the reads of the big window are done
         const int r = l >> 1, h = l & 1;
-        const int y = sk_clip(mby * 16 + cy0 - kWin + r, ylo, yhi);
+        const int y = sk_clip(mby * 16 + by - kWin + r, ylo, yhi);
         const uint8_t* rowp = a.ref.y + (size_t)y * a.stride_y;
-        const int x0 = mbx * 16 + cx0 - kWin + 16 * h;
+        const int x0 = mbx * 16 + bx - kWin + 16 * h;
 #pragma unroll
         for (int k = 0; k < 5; k++) win[r * kWinWords + 4 * h + k] = load_ref4(rowp, x0 + 4 * k, a.stride_y);
+        wn = MeWin{win, kWinWords, kWin, bx, by};
+        wave_sync();
     }
-    wave_sync();
     const int ddx[4] = {0, -1, 1, 0}, ddy[4] = {-1, 0, 0, 1};
     for (int it = 0; it < a.me_iters; it++) {
+        // 4 SADs in two packed wave sums (independent chains); inside the window (the
+        // common case) they are LDS reads
+        uint32_t p[4];
+        bool in_r[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = bx + ddx[k], y = by + ddy[k];
+            in_r[k] = !(x < -R || x > R || y < -R || y > R);
+            p[k] = in_r[k] ? sad_lane(x, y) : 0u;
+        }
+        const uint32_t s01 = (uint32_t)wave_sum((int)(p[0] | (p[1] << 16)));
+        const uint32_t s23 = (uint32_t)wave_sum((int)(p[2] | (p[3] << 16)));
+        const int sds[4] = {(int)(s01 & 0xffff), (int)(s01 >> 16), (int)(s23 & 0xffff), (int)(s23 >> 16)};
         int nb = -1, ncost = bcost, nsad = 0;
-        // common case: the whole diamond lies in the LDS window -> 4 SADs in two
-        // packed wave sums (independent chains) instead of four sequential ones
-        bool all_in = true;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const int ox = bx + ddx[k] - cx0, oy = by + ddy[k] - cy0;
-            all_in = all_in && ox >= -kWin && ox <= kWin && oy >= -kWin && oy <= kWin;
-        }
-        if (all_in) {
-            uint32_t p[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) p[k] = win_sad_lane(win, sw, bx + ddx[k] - cx0, by + ddy[k] - cy0);
-            const uint32_t s01 = (uint32_t)wave_sum((int)(p[0] | (p[1] << 16)));
-            const uint32_t s23 = (uint32_t)wave_sum((int)(p[2] | (p[3] << 16)));
-            const int sds[4] = {(int)(s01 & 0xffff), (int)(s01 >> 16), (int)(s23 & 0xffff), (int)(s23 >> 16)};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                int x = bx + ddx[k], y = by + ddy[k];
-                if (x < -R || x > R || y < -R || y > R) continue;
-                int c = sds[k] + lam * (sk_se_bits(4 * x) + sk_se_bits(4 * y));
-                if (c < ncost) { ncost = c; nb = k; nsad = sds[k]; }
-            }
-            if (nb < 0) break;
-            bx += ddx[nb]; by += ddy[nb]; bcost = ncost; bsad = nsad;
-            continue;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
+            if (!in_r[k]) continue;
             int x = bx + ddx[k], y = by + ddy[k];
-            if (x < -R || x > R || y < -R || y > R) continue;
-            const int ox = x - cx0, oy = y - cy0;
-            int sd = (ox >= -kWin && ox <= kWin && oy >= -kWin && oy <= kWin)
-                         ? win_sad(win, sw, ox, oy)
-                         : me_sad(a, a.ref.y, sw, mbx, mby, x, y, ylo, yhi);
-            int c = sd + lam * (sk_se_bits(4 * x) + sk_se_bits(4 * y));
-            if (c < ncost) { ncost = c; nb = k; nsad = sd; }
+            int c = sds[k] + lam * (sk_se_bits(4 * x) + sk_se_bits(4 * y));
+            if (c < ncost) { ncost = c; nb = k; nsad = sds[k]; }
         }
         if (nb < 0) break;
         bx += ddx[nb]; by += ddy[nb]; bcost = ncost; bsad = nsad;
@@ -577,6 +592,23 @@ __global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
     }
 }
 
+// K4 without the exhaustive search (me_full off): one single-wave workgroup per MB.
+__global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
+    __shared__ uint32_t win[32 * kWinWords];
+    int nmb = a.mb_w * a.mb_h;
+    int idx = xcd_remap(blockIdx.x, gridDim.x);
+    if (idx >= nmb) return;
+    int mbx = idx % a.mb_w, mby = idx / a.mb_w;
+    const SliceTask t = a.tasks[mby / a.rows_per_slice];
+    if (t.action != ACT_P && t.action != ACT_I) return;
+    int l = lane_id();
+    uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
+                                                     mbx * 16 + (l & 3) * 4);
+    const bool have_fs = a.me_full && t.action == ACT_P && a.mb_dirty[idx];   // a winner left in fs_mv
+    const int fsx = have_fs ? a.fs_mv[2 * idx] : 0, fsy = have_fs ? a.fs_mv[2 * idx + 1] : 0;
+    me_search_mb(a, t, idx, mbx, mby, sw, have_fs, fsx, fsy, win, false);
+}
+
 // ---------------------------------------------------------------------------
 // K4a: exhaustive +-16 integer search on the matrix cores, one wave per dirty MB
 // of a P slice (csrc/codec/h264_core.h fs_key; CPU reference full_search).
@@ -589,7 +621,7 @@ __global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
 // others are all-zero in S) = 32 MFMAs per MB. A fragments are unaligned 16-byte
 // runs of a window row (5 LDS dwords + v_alignbyte), B fragments aligned block rows.
 // sum w'^2 per candidate comes from separable 16-tap box sums in LDS. The wave
-// min of fs_key gives the winner, which k_motion_search adds as a predictor.
+// min of fs_key gives the winner, which the search adds as a predictor.
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 // LDS row strides are padded against bank conflicts (MI355X_MICROARCH.md §LDS lane
@@ -598,45 +630,27 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 // on distinct banks), block rows 5 dwords (B fragments read ~17 different rows per
 // group), box-sum rows 36 ints (16-B aligned int4 stores of 8 consecutive lanes cover 32
 // distinct banks; the fs_key reads are int4 too). 1512 -> 584 modelled LDS cycles per MB.
-__global__ __launch_bounds__(256) void k_me_mfma(FrameArgs a) {
+// The search's SAD reads (win_sad_lane: 8 rows x 4 dwords per 32-lane group) take 2 cycles
+// per group at 13 dwords, as they do in the small window at 10, and 1 at 12: 4 modelled
+// cycles per SAD against 48 saved on the row loads, so the odd stride stays.
+constexpr int kFsBlkWords = 5;             // padded block row stride
+constexpr int kFsSqInts = 2 * kFsR + 4;    // padded box-sum row stride (ints)
+
+// Fills the wave's window `win` and returns the minimum fs_key (the same in every lane).
+// The window stays valid afterwards.
+__device__ __forceinline__ uint64_t fs_search(const FrameArgs& a, uint32_t* win, uint32_t* blk, int* sq, int mbx, int mby,
+                                              uint32_t sw, int ylo, int yhi) {
     constexpr int WW = kFsWin / 4;                       // window dwords per row (12)
-    constexpr int WP = WW + 1;                           // padded window row stride
-    constexpr int BP = 5;                                // padded block row stride
-    constexpr int SP = 2 * kFsR + 4;                     // padded box-sum row stride (ints)
-    __shared__ uint32_t win_s[4][kFsWin * WP];           // raw reference window per wave
-    __shared__ uint32_t blk_s[4][16 * BP];               // raw 16x16 source block
-    __shared__ __align__(16) int sq_s[4][kFsWin * SP];   // row box sums of w'^2, then |r_d|^2
-    const int w = threadIdx.x >> 6, l = lane_id();
-    const int nmb = a.mb_w * a.mb_h;
-    const int idx = xcd_remap(blockIdx.x, gridDim.x) * 4 + w;
-    if (idx >= nmb) return;
-    const int mbx = idx % a.mb_w, mby = idx / a.mb_w;
-    const SliceTask t = a.tasks[mby / a.rows_per_slice];
-    if (t.action != ACT_P || !a.mb_dirty[idx]) return;
-    const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
-    {   // exact match at the MB's previous vector: skip the search (CPU: same rule)
-        const int R = a.me_range;
-        const int px = sk_clip(a.mvfield[2 * idx], -R, R), py = sk_clip(a.mvfield[2 * idx + 1], -R, R);
-        const uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
-                                                               mbx * 16 + (l & 3) * 4);
-        if (me_sad(a, a.ref.y, sw, mbx, mby, px, py, ylo, yhi) == 0) {
-            if (l == 0) {
-                a.fs_mv[2 * idx] = (int16_t)px;
-                a.fs_mv[2 * idx + 1] = (int16_t)py;
-            }
-            return;
-        }
-    }
-    uint32_t* win = win_s[w];
-    uint32_t* blk = blk_s[w];
-    int* sq = sq_s[w];
+    constexpr int WP = kFsWinWords;                      // padded window row stride
+    constexpr int BP = kFsBlkWords;
+    constexpr int SP = kFsSqInts;
+    const int l = lane_id();
     for (int i = l; i < kFsWin * WW; i += 64) {
         const int wy = i / WW, q = i - wy * WW;
         const int y = sk_clip(mby * 16 - kFsR + wy, ylo, yhi);
         win[wy * WP + q] = load_ref4(a.ref.y + (size_t)y * a.stride_y, mbx * 16 - kFsR + 4 * q, a.stride_y);
     }
-    blk[(l >> 2) * BP + (l & 3)] = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
-                                                                     mbx * 16 + (l & 3) * 4);
+    blk[(l >> 2) * BP + (l & 3)] = sw;
     wave_sync();
     // |r_d|^2: 16-tap row box sums (lane = window row), then 16-tap column sums in
     // place. Each lane loads its whole row / column into registers before it stores
@@ -737,10 +751,51 @@ __global__ __launch_bounds__(256) void k_me_mfma(FrameArgs a) {
         const uint64_t other = __shfl_xor(best, o);
         best = other < best ? other : best;
     }
-    if (l == 0) {
-        a.fs_mv[2 * idx] = (int16_t)fs_key_dx(best);
-        a.fs_mv[2 * idx + 1] = (int16_t)fs_key_dy(best);
+    return best;
+}
+
+// K4a + K4 in one dispatch (me_full on): four waves per workgroup, one macroblock each.
+// Phase 1, dirty MBs of P slices: the exhaustive search (skipped on an exact match at
+// the MB's previous vector); the winner stays in registers and goes to fs_mv (a
+// debug_buffer name of the CPU model). Phase 2, every MB of a P / I slice:
+// me_search_mb, which reads its SADs from the wave's phase-1 window where it can.
+__global__ __launch_bounds__(256) void k_me(FrameArgs a) {
+    __shared__ uint32_t win_s[4][kFsWin * kFsWinWords];       // raw reference window per wave
+    __shared__ uint32_t blk_s[4][16 * kFsBlkWords];           // raw 16x16 source block
+    __shared__ __align__(16) int sq_s[4][kFsWin * kFsSqInts]; // row box sums of w'^2, then |r_d|^2
+    static_assert(kFsWin * kFsWinWords >= 32 * kWinWords, "the small window lives in the wave's win_s region");
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const int nmb = a.mb_w * a.mb_h;
+    const int idx = xcd_remap(blockIdx.x, gridDim.x) * 4 + w;
+    if (idx >= nmb) return;
+    const int mbx = idx % a.mb_w, mby = idx / a.mb_w;
+    const SliceTask t = a.tasks[mby / a.rows_per_slice];
+    if (t.action != ACT_P && t.action != ACT_I) return;
+    const uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
+                                                           mbx * 16 + (l & 3) * 4);
+    bool have_fs = false, big = false;
+    int fsx = 0, fsy = 0;
+    if (t.action == ACT_P && a.mb_dirty[idx]) {
+        have_fs = true;
+        const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
+        const int R = a.me_range;
+        const int px = sk_clip(a.mvfield[2 * idx], -R, R), py = sk_clip(a.mvfield[2 * idx + 1], -R, R);
+        if (me_sad(a, a.ref.y, sw, mbx, mby, px, py, ylo, yhi) == 0) {
+            // exact match at the MB's previous vector: skip the search (CPU: same rule)
+            fsx = px;
+            fsy = py;
+        } else {
+            const uint64_t best = fs_search(a, win_s[w], blk_s[w], sq_s[w], mbx, mby, sw, ylo, yhi);
+            fsx = __builtin_amdgcn_readfirstlane(fs_key_dx(best));
+            fsy = __builtin_amdgcn_readfirstlane(fs_key_dy(best));
+            big = true;
+        }
+        if (l == 0) {
+            a.fs_mv[2 * idx] = (int16_t)fsx;
+            a.fs_mv[2 * idx + 1] = (int16_t)fsy;
+        }
     }
+    me_search_mb(a, t, idx, mbx, mby, sw, have_fs, fsx, fsy, win_s[w], big);
 }
 
 // Frame controller on the GPU (one workgroup): commits the previous frame's
@@ -871,13 +926,19 @@ __global__ __launch_bounds__(64) void k_rc_qp(FrameArgs a) {
     for (int s = threadIdx.x; s < a.num_slices; s += 64) a.tasks_host[s].qp = a.tasks[s].qp;
 }
 
-// per_slice > 0: sizes are per NAL, per_slice NALs per slice, counted for coded slices
-__global__ __launch_bounds__(64) void k_rc_account(FrameArgs a, const int* sizes, int n, int stride, int per_slice) {
+// K10 accounting of the frame just coded, one wave. per_slice > 0: sizes are per NAL,
+// per_slice NALs per slice, counted for coded slices.
+__device__ __forceinline__ void rc_account_wave(const FrameArgs& a, const int* sizes, int n, int stride, int per_slice) {
     long long b = 0;
-    for (int i = threadIdx.x; i < n; i += 64)
+    for (int i = lane_id(); i < n; i += 64)
         if (!per_slice || i % per_slice < slice_nals(a, a.tasks[i / per_slice])) b += sizes[(size_t)i * stride];
     for (int o = 32; o > 0; o >>= 1) b += __shfl_down(b, o);
-    if (threadIdx.x == 0) rc_account(*a.rc, 8 * b);
+    if (lane_id() == 0) rc_account(*a.rc, 8 * b);
+}
+
+// K10 accounting of the HEVC / AV1 back ends (the H.264 chain does it in k_ep_count)
+__global__ __launch_bounds__(64) void k_rc_account(FrameArgs a, const int* sizes, int n, int stride, int per_slice) {
+    rc_account_wave(a, sizes, n, stride, per_slice);
 }
 
 // K10 CBR guard after k_slice_scan: every workgroup (one per slice) evaluates the same
@@ -2586,14 +2647,16 @@ __global__ __launch_bounds__(256) void k_cavlc(FrameArgs a) {
 //                 NAL header) written straight into the host-mapped slot
 //   k_mb_concat   one wave per MB: shifts its CAVLC words into the slice RBSP
 //                 (plain stores; atomicOr only on the two edge words it shares)
-//   k_ep_nz / k_ep_count / k_ep_write   4 KiB tiles of every slice in parallel:
+//   k_ep_count / k_ep_write   4 KiB tiles of every slice in parallel:
 //                 emulation prevention (7.4.1) — a 0x03 goes before byte i iff
 //                 b_i <= 3 and the zero run z(i) right before i is even and >= 2,
 //                 which only depends on the input bytes; a tile needs the last
-//                 non-zero byte before it (prefix max of k_ep_nz) and the number
-//                 of insertions before it (prefix sum of k_ep_count). k_ep_write
-//                 stages its output in LDS, streams it to host memory with 16-byte
-//                 stores and self-cleans the RBSP words it consumed.
+//                 non-zero byte before it (its carry: k_ep_count looks backwards
+//                 from the tile, codec/h264_ep.h) and the number of insertions
+//                 before it (prefix sum of k_ep_count). k_ep_write stages its
+//                 output in LDS, streams it to host memory with 16-byte stores and
+//                 self-cleans the RBSP words it consumed. k_ep_count also does the
+//                 frame's K10 accounting (one wave of its first workgroup).
 constexpr int kTile = 4096;
 
 __global__ __launch_bounds__(256) void k_slice_scan(FrameArgs a) {
@@ -2736,42 +2799,16 @@ __global__ __launch_bounds__(256) void k_mb_concat(FrameArgs a) {
     }
 }
 
-__device__ __forceinline__ uint8_t rbsp_byte(uint32_t word, int q) { return (uint8_t)(word >> (24 - 8 * q)); }
+__device__ __forceinline__ uint8_t rbsp_byte(uint32_t word, int q) { return ep_rbsp_byte(word, q); }
 
 // EP kernels: grid (tile, slice); a block loops over the slice's NALs (one for every
 // slice but the sub-sliced I ones, so P pictures launch no per-NAL blocks).
-__global__ __launch_bounds__(256) void k_ep_nz(FrameArgs a) {
-    __shared__ int red[4];
-    const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-    const int nn = slice_nals(a, a.tasks[s]);
-    for (int j = 0; j < nn; j++) {
-    const int nal = s * a.nal_per_slice + j;
-    const int n = a.slice_info[4 * nal];
-    const int t0 = t * kTile;
-    if (t0 >= n) continue;
-    const uint32_t* rbsp = nal_rbsp(a, s, j);
-    const int i0 = t0 + tid * 16;
-    int lastnz = -1;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int iq = i0 + 4 * q;
-        const uint32_t wd = iq < n ? rbsp[iq >> 2] : 0u;
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-            if (iq + b < n && rbsp_byte(wd, b)) lastnz = iq + b;
-    }
-    for (int o = 32; o > 0; o >>= 1) lastnz = max(lastnz, __shfl_down(lastnz, o));
-    if (lane_id() == 0) red[tid >> 6] = lastnz;
-    __syncthreads();
-    if (tid == 0) a.tile_nz[nal * a.max_tiles + t] = max(max(red[0], red[1]), max(red[2], red[3]));
-    __syncthreads();
-    }
-}
-
-// Per-thread EP decisions for 16 bytes starting at i0; `carry` = last non-zero
-// byte index before the tile. Returns the insertion count; bytes and insertion
+// Per-thread EP decisions for 16 bytes starting at i0; `carry()` = last non-zero
+// byte index before the tile, asked for after the workgroup barrier (k_ep_count
+// hands it over through LDS). Returns the insertion count; bytes and insertion
 // mask through the out parameters.
-__device__ __forceinline__ int ep_thread(const uint32_t* rbsp, int n, int t0, int carry, int* scan_lds,
+template <class Carry>
+__device__ __forceinline__ int ep_thread(const uint32_t* rbsp, int n, int t0, Carry carry, int* scan_lds,
                                          uint8_t* by, uint32_t* insmask) {
     const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
     const int i0 = t0 + tid * 16;
@@ -2791,7 +2828,7 @@ __device__ __forceinline__ int ep_thread(const uint32_t* rbsp, int n, int t0, in
     if (ln == 0) ex = -1;
     if (ln == 63) scan_lds[wv] = incl;
     __syncthreads();
-    int prev = carry;
+    int prev = carry();
     for (int k = 0; k < wv; k++) prev = max(prev, scan_lds[k]);
     prev = max(prev, ex);
     int ins = 0;
@@ -2812,16 +2849,20 @@ __device__ __forceinline__ int ep_thread(const uint32_t* rbsp, int n, int t0, in
     return ins;
 }
 
-__device__ __forceinline__ int tile_carry(const FrameArgs& a, int nal, int t) {
-    int c = -1;  // the NAL header byte before the RBSP is non-zero
-    for (int k = 0; k < t; k++) c = max(c, a.tile_nz[nal * a.max_tiles + k]);
-    return c;
-}
-
+// The carry of every tile (h264_ep.h) is taken here and stored, not in k_ep_write:
+// k_ep_write clears the RBSP words of its own tile, so a tile that looked backwards
+// there could read words its predecessor tile has already zeroed. Here every
+// workgroup only reads bytes that the kernels before this one finished; k_ep_write
+// loads the stored carry.
 __global__ __launch_bounds__(256) void k_ep_count(FrameArgs a) {
     __shared__ int scan_lds[4];
     __shared__ int red[4];
+    __shared__ int sh_carry;
     const int s = blockIdx.y, t = blockIdx.x;
+    // K10: the slice sizes are final since k_slice_scan and nothing else in this kernel
+    // touches *a.rc; before the NAL loop, so that an uncoded slice 0 does not skip it
+    if (s == 0 && t == 0 && threadIdx.x < 64)
+        rc_account_wave(a, a.slice_info, a.num_slices * a.nal_per_slice, 4, a.nal_per_slice);
     const int nn = slice_nals(a, a.tasks[s]);
     for (int j = 0; j < nn; j++) {
         const int nal = s * a.nal_per_slice + j;
@@ -2829,9 +2870,16 @@ __global__ __launch_bounds__(256) void k_ep_count(FrameArgs a) {
         const int t0 = t * kTile;
         if (t0 >= n) continue;
         const uint32_t* rbsp = nal_rbsp(a, s, j);
+        if (threadIdx.x < 64) {
+            const int c = ep_tile_carry(rbsp, t0, lane_id(), 64, [](bool p) { return (uint64_t)__ballot(p); });
+            if (threadIdx.x == 0) {
+                sh_carry = c;
+                a.tile_carry[nal * a.max_tiles + t] = c;
+            }
+        }
         uint8_t by[16];
         uint32_t mask;
-        int ins = ep_thread(rbsp, n, t0, tile_carry(a, nal, t), scan_lds, by, &mask);
+        int ins = ep_thread(rbsp, n, t0, [&] { return sh_carry; }, scan_lds, by, &mask);
         for (int o = 32; o > 0; o >>= 1) ins += __shfl_down(ins, o);
         if (lane_id() == 0) red[threadIdx.x >> 6] = ins;
         __syncthreads();
@@ -2873,7 +2921,8 @@ __global__ __launch_bounds__(256) void k_ep_write(FrameArgs a) {
     uint32_t* rbsp = nal_rbsp(a, s, j);
     uint8_t by[16];
     uint32_t mask;
-    const int ins = ep_thread(rbsp, n, t0, tile_carry(a, nal, t), scan_lds, by, &mask);
+    const int carry = a.tile_carry[nal * a.max_tiles + t];   // from k_ep_count: this kernel clears RBSP words
+    const int ins = ep_thread(rbsp, n, t0, [&] { return carry; }, scan_lds, by, &mask);
     int tile_ins;
     const int ex = block_excl_scan<4>(ins, wave_tot, &tile_ins);
     const int i0 = t0 + tid * 16;
@@ -3282,8 +3331,8 @@ void launch_convert_damage(const FrameArgs& a, hipStream_t s) {
 void launch_frontend(const FrameArgs& a, hipStream_t s) {
     int nmb = a.mb_w * a.mb_h;
     hipLaunchKernelGGL(k_plan, dim3(1), dim3(256), 0, s, a);
-    if (a.me_full) hipLaunchKernelGGL(k_me_mfma, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_motion_search, dim3(nmb), dim3(64), 0, s, a);
+    if (a.me_full) hipLaunchKernelGGL(k_me, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_motion_search, dim3(nmb), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_decide, dim3(a.num_slices), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_rc_qp, dim3(1), dim3(64), 0, s, a);
     // K4c quarter-pel refinement (H.264 and HEVC; the HEVC back end codes the vectors
@@ -3327,10 +3376,8 @@ void launch_encode(const FrameArgs& a, hipStream_t s, bool guard) {
     }
     hipLaunchKernelGGL(k_mb_concat, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
     const dim3 tiles(a.max_tiles, a.num_slices);
-    hipLaunchKernelGGL(k_ep_nz, tiles, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_ep_count, tiles, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_ep_write, tiles, dim3(256), 0, s, a);
-    launch_rc_account(a, a.slice_info, a.num_slices * a.nal_per_slice, 4, a.nal_per_slice, s);
+    hipLaunchKernelGGL(k_ep_write, tiles, dim3(256), 0, s, a);   // K10 accounting: inside k_ep_count
 }
 
 void launch_commit(const FrameArgs& a, hipStream_t s) {

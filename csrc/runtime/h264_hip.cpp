@@ -621,7 +621,7 @@ class HipBackend : public EncoderBackend {
         a.mb_off = dmalloc<int>(nmb);
         a.slice_info = dmalloc<int>(4 * (size_t)ns * a.nal_per_slice);
         a.max_tiles = (a.rbsp_slot_words * 4 + 4095) / 4096;
-        a.tile_nz = dmalloc<int>((size_t)ns * a.nal_per_slice * a.max_tiles);
+        a.tile_carry = dmalloc<int>((size_t)ns * a.nal_per_slice * a.max_tiles);
         a.tile_ins = dmalloc<int>((size_t)ns * a.nal_per_slice * a.max_tiles);
         // worst case: header + SPS/PPS + 3/2 emulation-prevention growth, 64-byte multiple
         size_t slot = ((size_t)a.rbsp_slot_words * 4 * 3 / 2 + 1024 + 63) & ~(size_t)63;

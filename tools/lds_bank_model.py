@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""LDS bank-conflict model of k_me_mfma's accesses (lane groups and bank rules of
+"""LDS bank-conflict model of k_me's accesses (lane groups and bank rules of
 MI355X_MICROARCH.md §LDS): prints modelled LDS cycles per MB for candidate row strides
 (box-sum rows S, window rows WW, block rows BS)."""
 # LDS bank model of MI355X_MICROARCH.md §LDS: per instruction lane groups, bank = dword mod nb
@@ -62,6 +62,15 @@ def analyse(S, WW, BS):
                     ad[l] = (src if 0 <= src < 16 else 0)*BS + q
                 c += cycles(ad, G32, 32, 1)
     out['B_frag'] = (c, 12*2*4*2)
+    # (g) one search SAD read from the window (win_sad_lane: lane -> row l>>2, dword l&3 of the
+    # 16x16 block at offset (ox, oy), aligned pair w[0], w[1]), averaged over offsets: x 10
+    offs = [(ox, oy) for ox in range(-16, 17) for oy in (-16, 0, 5, 16)]
+    c = 0
+    for ox, oy in offs:
+        for k in range(2):
+            ad = {l: ((l >> 2) + oy + 16)*WW + (((l & 3)*4 + ox + 16) >> 2) + k for l in range(64)}
+            c += cycles(ad, G32, 32, 1)
+    out['sad_read_x10'] = (round(10*c/len(offs)), 10*2*2)
     return out
 for S, WW, BS in [(32,12,4),(36,12,4),(36,13,5),(44,13,5),(33,13,5),(40,13,5),(52,13,5),(36,12,5)]:
     o = analyse(S, WW, BS)
