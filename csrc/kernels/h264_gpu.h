@@ -34,7 +34,7 @@ struct FrameArgs {
     StripeState* plan_state;    // [num_slices + 1] controller state (last = picture state)
     int* plan_ctl;              // [0] keyframe requests seen, [1] frames planned (0 = first frame)
     const int* key_seq_host;    // host-mapped: [0] keyframe request counter, [1] qp, [2] paint qp (0 = config)
-    int* key_dev;               // [6] k_plan's device copy of the snapshot (read by k_rc_qp)
+    int* key_dev;               // [6] device copy of the snapshot, left by the damage kernel (read by k_plan, k_rc_qp)
     PlanConfig plan_cfg;
     SliceTask* tasks;      // [num_slices]
     MeResult* me;          // [num_mbs]
@@ -56,7 +56,7 @@ struct FrameArgs {
     int param_set_stride;
     uint8_t* host_out;     // host-mapped packet slots [num_slices][out_slot_bytes]
     int* host_size;        // host-mapped [num_slices] bytes in each slot
-    int* frame_params_dev;           // device: [0] = frame_id (loaded by k_plan)
+    int* frame_params_dev;           // device: [0] = frame_id (loaded by the damage kernel)
     const int* frame_params_host;    // host-mapped source
     SliceTask* tasks_host;           // host-mapped: final slice decisions (written by k_decide)
     unsigned long long* dbg;  // optional s_memtime stamps (SK_STAMPS=1), else nullptr
@@ -90,7 +90,10 @@ struct FrameArgs {
     int yuv_fmt;
 };
 
-void launch_convert_damage(const FrameArgs& a, hipStream_t s);   // K1 + K3, or k_yuv_damage for planar input
+// K1 + K3, or k_yuv_damage for planar input. Also fetches the frame's host-mapped words
+// (key_seq_host, frame_params_host) into key_dev / frame_params_dev, which k_plan and the
+// kernels after it read: every codec calls it first, ahead of launch_frontend / launch_encode.
+void launch_convert_damage(const FrameArgs& a, hipStream_t s);
 // k_plan and everything after it; guard: CBR overflow guard + gated second coding pass
 void launch_encode(const FrameArgs& a, hipStream_t s, bool guard = false);
 // k_plan, motion search and scene-cut decisions only (the HEVC back end follows it)

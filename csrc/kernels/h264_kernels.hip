@@ -7,11 +7,14 @@
 // quad vertically with DPP quad-permutes (no LDS round trip).
 //
 // Stages (all bit-exact with the CPU reference csrc/codec/h264_cpu.cpp):
-//   k_convert_damage  K1+K3  BGRx -> NV12-planar YUV 4:2:0 + per-MB damage bits
+//   k_convert_damage  K1+K3  BGRx -> NV12-planar YUV 4:2:0 + per-MB damage bits; its first workgroup
+//                            fetches the frame's host-mapped words into device memory
+//   k_plan                   stripe controller (reads device memory only)
 //   k_me              K4a+K4 exhaustive +-16 search (int8 MFMA cross-correlation, SSD), then
 //                            candidate + diamond integer search (v_sad_u8) on the same LDS window
 //   k_motion_search   K4     the candidate + diamond search alone (me_full off)
 //   k_decide                 per-slice scene-cut decision
+//   k_rc_qp           K10    frame QP: one lane's serial chain, on LDS copies of its inputs
 //   k_code_inter      K6     MC, transform, quant/decimation, QP escalation, recon
 //   k_code_intra      K5+K6  Intra16x16 wavefront (one wave per MB row, lag 2)
 //   k_cavlc           K8     per-MB CAVLC: lanes code residual blocks in parallel,
@@ -240,6 +243,25 @@ struct StageBitWriter {
 // thread = 8 x 2 pixels (4 chroma quads) with 16-byte BGRx loads. Per-MB dirty
 // flags go to mb_dirty; the stripe flag is one plain store per workgroup into
 // host-mapped memory (no same-line atomics, no device->host copy).
+//
+// The host-mapped words of the frame (keyframe / QP / rate snapshot for k_plan and k_rc_qp,
+// frame id for k_slice_scan) are fetched by the first workgroup of the damage kernel: ten
+// lanes, one PCIe round trip that completes while the workgroup converts, stored to device
+// memory at its end. k_plan, a single workgroup on the frame's critical path, then reads
+// device memory only.
+__device__ __forceinline__ int host_words_load(const FrameArgs& a) {
+    const int tid = threadIdx.x;
+    if (blockIdx.x != 0 || blockIdx.y != 0 || tid >= 10) return 0;
+    return __hip_atomic_load(tid < 6 ? a.key_seq_host + tid : a.frame_params_host + (tid - 6), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void host_words_store(const FrameArgs& a, int v) {
+    const int tid = threadIdx.x;
+    if (blockIdx.x != 0 || blockIdx.y != 0 || tid >= 10) return;
+    if (tid < 6) a.key_dev[tid] = v;
+    else a.frame_params_dev[tid - 6] = v;
+}
+
 __device__ __forceinline__ uint32_t bgrx_px(const uint8_t* row, int x, int W) {
     return *reinterpret_cast<const uint32_t*>(row + 4 * sk_min(x, W - 1));
 }
@@ -247,6 +269,7 @@ __device__ __forceinline__ uint32_t bgrx_px(const uint8_t* row, int x, int W) {
 __global__ __launch_bounds__(256) void k_convert_damage(FrameArgs a) {
     __shared__ int mbd[16];
     const int t = threadIdx.x;
+    const int host_words = host_words_load(a);
     if (t < 16) mbd[t] = 0;
     __syncthreads();
     const int item = t & 31, qr = t >> 5;          // 32 items across (8 px each), 8 quad rows
@@ -326,6 +349,7 @@ __global__ __launch_bounds__(256) void k_convert_damage(FrameArgs a) {
     }
     if (__syncthreads_or(t < 16 && mbd[t] && mbx0 + t < a.mb_w) && t == 0)
         a.stripe_dirty[mby / a.rows_per_slice] = 1;
+    host_words_store(a, host_words);
 }
 
 // K3 for planar 4:2:0 input (GStreamer NV12 / I420, h264_frame.h YuvInput): the staged
@@ -335,6 +359,7 @@ __global__ __launch_bounds__(256) void k_convert_damage(FrameArgs a) {
 __global__ __launch_bounds__(256) void k_yuv_damage(FrameArgs a) {
     __shared__ int mbd[16];
     const int t = threadIdx.x;
+    const int host_words = host_words_load(a);
     if (t < 16) mbd[t] = 0;
     __syncthreads();
     const int item = t & 31, qr = t >> 5;
@@ -389,6 +414,7 @@ __global__ __launch_bounds__(256) void k_yuv_damage(FrameArgs a) {
     }
     if (__syncthreads_or(t < 16 && mbd[t] && mbx0 + t < a.mb_w) && t == 0)
         a.stripe_dirty[mby / a.rows_per_slice] = 1;
+    host_words_store(a, host_words);
 }
 
 // ---------------------------------------------------------------------------
@@ -817,13 +843,10 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
             for (int s = tid; s < ns; s += 256) commit_stripe(st[s], a.tasks[s].final_action, a.plan_cfg.num_refs);
         }
     }
-    // host overrides (host-mapped snapshot): one round trip, six lanes in parallel; the
-    // device copy is what k_rc_qp reads later in the frame
+    // host overrides: the device copy of the host-mapped snapshot that the damage kernel
+    // left (host_words_store), which k_rc_qp reads too
     __shared__ int hk[6];
-    if (tid < 6) {
-        hk[tid] = __hip_atomic_load(a.key_seq_host + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        a.key_dev[tid] = hk[tid];
-    }
+    if (tid < 6) hk[tid] = a.key_dev[tid];
     __syncthreads();
     const int kq = hk[0];
     const bool key = kq != a.plan_ctl[0];
@@ -854,7 +877,6 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
         a.plan_ctl[0] = kq;
         a.plan_ctl[1] = 1;
     }
-    if (tid < 4) a.frame_params_dev[tid] = a.frame_params_host[tid];
 }
 
 // One workgroup per slice: scene-cut decision from the per-MB ME results.
@@ -894,15 +916,15 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
 
 // K10: frame QP from the complexity sums (same rc_apply as the CPU controller).
 // Host overrides: key_seq_host[1] qp, [3] rc mode, [4] kbps, [5] change counter.
-__device__ void rc_qp_serial(const FrameArgs& a) {
-    RcState& rc = *a.rc;
-    const int seq = a.key_dev[5];   // k_plan's copy of the host snapshot
+// `key`: the device copy of the host snapshot; `sums`: rc_slice ([slice][2]).
+__device__ void rc_qp_serial(const FrameArgs& a, const int* key, RcState& rc, SliceTask* tasks, const long long* sums) {
+    const int seq = key[5];
     int plan_qp = a.plan_cfg.qp;
-    const int qo = a.key_dev[1];
+    const int qo = key[1];
     if (qo > 0) plan_qp = qo;
     if (seq != rc.seq) {   // set_rate() from the host: re-initialise, keep the model if the mode stays
-        const int mode = a.key_dev[3];
-        const int kbps = a.key_dev[4];
+        const int mode = key[3];
+        const int kbps = key[4];
         const RcState old = rc;
         rc_init(rc, mode, plan_qp, kbps, (float)a.rc_fps, a.W * a.H, old.vbv_ms, old.codec);
         if (old.mode == mode)
@@ -916,14 +938,41 @@ __device__ void rc_qp_serial(const FrameArgs& a) {
         rc.seq = seq;
     }
     rc.base_qp = plan_qp;
-    rc_apply(rc, a.tasks, a.rc_slice, a.rc_slice + 1, a.num_slices, a.mb_w, plan_qp, 2);
+    rc_apply(rc, tasks, sums, sums + 1, a.num_slices, a.mb_w, plan_qp, 2);
 }
+// rc_qp_serial is one lane's chain of dependent reads of the tasks, the sums and the
+// controller state (12.7 us median out of device memory under the 8-session load): the wave
+// copies them to LDS in parallel (up to kRcLdsSlices slices), lane 0 runs the chain there,
+// and the state and the slice QPs, all the chain changes, go back in parallel.
+constexpr int kRcLdsSlices = 128;
 __global__ __launch_bounds__(64) void k_rc_qp(FrameArgs a) {
-    if (threadIdx.x == 0) rc_qp_serial(a);
+    __shared__ long long sums_l[2 * kRcLdsSlices];
+    __shared__ SliceTask tasks_l[kRcLdsSlices];
+    __shared__ RcState rc_l;
+    __shared__ int key_l[6];
+    static_assert(sizeof(RcState) % 4 == 0 && sizeof(SliceTask) % 4 == 0, "dword copies");
+    const int ns = a.num_slices, l = threadIdx.x;
+    const bool in_lds = ns <= kRcLdsSlices;
+    if (in_lds) {
+        for (int i = l; i < ns * (int)(sizeof(SliceTask) / 4); i += 64)
+            reinterpret_cast<uint32_t*>(tasks_l)[i] = reinterpret_cast<const uint32_t*>(a.tasks)[i];
+        for (int i = l; i < 2 * ns; i += 64) sums_l[i] = a.rc_slice[i];
+        if (l < (int)(sizeof(RcState) / 4)) reinterpret_cast<uint32_t*>(&rc_l)[l] = reinterpret_cast<const uint32_t*>(a.rc)[l];
+        if (l < 6) key_l[l] = a.key_dev[l];
+    }
     __syncthreads();
+    if (l == 0) {
+        if (in_lds) rc_qp_serial(a, key_l, rc_l, tasks_l, sums_l);
+        else rc_qp_serial(a, a.key_dev, *a.rc, a.tasks, a.rc_slice);
+    }
+    __syncthreads();
+    if (in_lds) {
+        if (l < (int)(sizeof(RcState) / 4)) reinterpret_cast<uint32_t*>(a.rc)[l] = reinterpret_cast<const uint32_t*>(&rc_l)[l];
+        for (int s = l; s < ns; s += 64) a.tasks[s].qp = tasks_l[s].qp;
+    }
     // the slice QPs to the host-mapped task copies, one lane per slice (uncached PCIe
     // writes: one wave-wide burst instead of a serial loop on lane 0)
-    for (int s = threadIdx.x; s < a.num_slices; s += 64) a.tasks_host[s].qp = a.tasks[s].qp;
+    for (int s = l; s < ns; s += 64) a.tasks_host[s].qp = in_lds ? tasks_l[s].qp : a.tasks[s].qp;
 }
 
 // K10 accounting of the frame just coded, one wave. per_slice > 0: sizes are per NAL,
@@ -941,13 +990,16 @@ __global__ __launch_bounds__(64) void k_rc_account(FrameArgs a, const int* sizes
     rc_account_wave(a, sizes, n, stride, per_slice);
 }
 
-// K10 CBR guard after k_slice_scan: every workgroup (one per slice) evaluates the same
-// overflow test on the frame's payload; on a redo, workgroup 0 moves the slice QPs
-// (rc_redo) and raises the flag for the gated second pass, and each workgroup clears
-// the header / trailing bits the first k_slice_scan left in its RBSP slot.
+// K10 CBR guard after k_slice_scan, one workgroup: the overflow test on the frame's
+// payload; on a redo it moves the slice QPs (rc_redo) and raises the flag for the gated
+// second pass, whose k_slice_scan first clears the header / trailing bits the first one
+// left in its RBSP slot. (Clearing here, per slice, from a test every workgroup repeated,
+// went wrong in two ways: a step that rc_redo does not apply - the frame already at the
+// top QP - cleared slots that no second pass filled again, and a workgroup that evaluated
+// the step after rc_redo had counted the pass saw none and kept its stale bits.)
 __global__ __launch_bounds__(256) void k_rc_guard(FrameArgs a) {
     __shared__ long long part[4];
-    const int s = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     long long b = 0;
     for (int i = tid; i < a.num_slices; i += 256) {
         const int nn = slice_nals(a, a.tasks[i]);
@@ -956,23 +1008,12 @@ __global__ __launch_bounds__(256) void k_rc_guard(FrameArgs a) {
     for (int o = 32; o > 0; o >>= 1) b += __shfl_down(b, o);
     if ((tid & 63) == 0) part[tid >> 6] = b;
     __syncthreads();
+    if (tid != 0) return;
     const long long bits = 8 * (part[0] + part[1] + part[2] + part[3]);
-    // rc_redo changes only cur_qp / redos / tasks, none of which rc_redo_step reads:
-    // every workgroup takes the same decision whatever the order
-    const int step = rc_redo_step(*a.rc, bits);
-    if (s == 0 && tid == 0) {
-        const int applied = step ? rc_redo(*a.rc, a.tasks, a.num_slices, bits) : 0;
-        *a.rc_redo = applied ? 1 : 0;
-        if (applied)
-            for (int i = 0; i < a.num_slices; i++) a.tasks_host[i].qp = a.tasks[i].qp;
-    }
-    if (!step || a.tasks[s].final_action == ACT_NONE) return;
-    const int nn = slice_nals(a, a.tasks[s]);
-    for (int j = 0; j < nn; j++) {
-        uint32_t* rbsp = nal_rbsp(a, s, j);
-        const int words = (a.slice_info[4 * (s * a.nal_per_slice + j)] + 3) / 4 + 1;
-        for (int i = tid; i < words; i += 256) rbsp[i] = 0u;
-    }
+    const int applied = rc_redo_step(*a.rc, bits) ? rc_redo(*a.rc, a.tasks, a.num_slices, bits) : 0;
+    *a.rc_redo = applied ? 1 : 0;
+    if (applied)
+        for (int i = 0; i < a.num_slices; i++) a.tasks_host[i].qp = a.tasks[i].qp;
 }
 
 // K10 per-frame cap of the HEVC / AV1 back ends: the frame's payload is the sum of
@@ -2670,6 +2711,14 @@ __global__ __launch_bounds__(256) void k_slice_scan(FrameArgs a) {
     const int fin = task.final_action;
     int* info = a.slice_info + 4 * nal;
     const int nn = slice_nals(a, task);
+    if (a.gate && info[0] > 0) {
+        // second pass: the first one's header and trailing bits are still in this NAL's RBSP
+        // (its size is in info[0]; the NALs of a slice are the same in both passes)
+        uint32_t* old = nal_rbsp(a, s, j);
+        const int words = (info[0] + 3) / 4 + 1;
+        for (int i = tid; i < words; i += 256) old[i] = 0u;
+        __syncthreads();
+    }
     if (j >= nn) {
         if (tid == 0) {
             info[0] = 0;
@@ -3369,7 +3418,7 @@ void launch_encode(const FrameArgs& a, hipStream_t s, bool guard) {
     if (a.aq_strength > 0) hipLaunchKernelGGL(k_aq, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
     launch_code(a, s);
     if (guard && a.rc_redo) {   // K10 CBR: VBV overflow -> one coarser pass (kernels exit early otherwise)
-        hipLaunchKernelGGL(k_rc_guard, dim3(a.num_slices), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_rc_guard, dim3(1), dim3(256), 0, s, a);
         FrameArgs b = a;
         b.gate = a.rc_redo;
         launch_code(b, s);

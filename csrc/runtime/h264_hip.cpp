@@ -1,10 +1,10 @@
 // HIP backend of the H.264 stripe encoder: owns the per-session HBM buffers,
 // the stream, pinned staging, and drives the gfx950 kernels
 // (csrc/kernels/h264_kernels.hip). Frame flow:
-//   H2D(BGRx) -> [K1/K3 convert+damage, k_plan (stripe controller on the GPU),
-//   K4 ME, decide, K6 inter, K5/K6 intra, K8 CAVLC, K9 slice assembly into
-//   host-mapped packet slots, commit] (one hipGraph per src/prev parity)
-//   -> one sync -> packets. No host decision sits inside a frame.
+//   H2D(BGRx) -> (overlay placement, only when it changed) -> [K1/K3 convert+damage,
+//   k_plan (stripe controller on the GPU), K4 ME, decide, K6 inter, K5/K6 intra, K8 CAVLC,
+//   K9 slice assembly into host-mapped packet slots, commit] (one hipGraph per src/prev
+//   parity) -> one sync -> packets. No host decision sits inside a frame.
 #include "encoder_iface.h"
 #include "trace.h"
 #include "../kernels/h264_gpu.h"
@@ -282,7 +282,17 @@ class HipBackend : public EncoderBackend {
         // before launch(n) applies to frame n even when frame n-1 has not planned yet
         for (int i = 0; i < 6; i++) h_key_snap_[p][i] = __atomic_load_n(&h_key_seq_[i], __ATOMIC_SEQ_CST);
         frame_of_[p] = staged_frame_;
-        memcpy(ov_params_host_[p], ov_pending_, sizeof(ov_pending_));   // read by this frame's graph
+        // Overlay placement of this frame: copied ahead of the graph, on the same stream (so
+        // behind the previous frame's graph, which read the old placement), and only when it
+        // differs from what the device holds; once more after the graphs were re-captured.
+        if (ov_resend_ || memcmp(ov_sent_, ov_pending_, sizeof(ov_pending_)) != 0) {
+            memcpy(ov_params_host_[ov_slot_], ov_pending_, sizeof(ov_pending_));
+            HIPCHECK(hipMemcpyAsync(ov_params_dev_, ov_params_host_[ov_slot_], sizeof(ov_pending_),
+                                    hipMemcpyHostToDevice, stream_));
+            memcpy(ov_sent_, ov_pending_, sizeof(ov_pending_));
+            ov_slot_ = (ov_slot_ + 1) % kOvStage;
+            ov_resend_ = false;
+        }
         if (!staged_on_main_) HIPCHECK(hipStreamWaitEvent(stream_, ev_copy_[p], 0));
         HIPCHECK(hipEventRecord(ev_[3 * p + 1], stream_));
         // convert/damage -> plan -> ME -> code -> CAVLC -> assembly -> commit: one graph,
@@ -554,8 +564,8 @@ class HipBackend : public EncoderBackend {
         for (int k = 0; k < kOverlaySlots; k++) {
             ov_img_dev_[k] = dmalloc<uint8_t>((size_t)kOverlayMaxDim * kOverlayMaxDim * 4);
             a.ov_img[k] = ov_img_dev_[k];
-            ov_params_host_[k] = hmalloc<OverlayParams>(kOverlaySlots);   // [parity][slot]
         }
+        for (auto& h : ov_params_host_) h = hmalloc<OverlayParams>(kOverlaySlots);
         ov_params_dev_ = dmalloc<OverlayParams>(kOverlaySlots);
         a.ov = ov_params_dev_;
         memset(ov_pending_, 0, sizeof(ov_pending_));
@@ -694,18 +704,17 @@ class HipBackend : public EncoderBackend {
     }
 
     void invalidate_graphs() {
+        ov_resend_ = true;
         for (auto* set : {graph_exec_, post_exec_})
             for (int i = 0; i < 2; i++)
                 if (set[i]) { hipGraphExecDestroy(set[i]); set[i] = nullptr; }
     }
 
     // part 0: convert/damage -> ... -> packets; part 1: commit (+ deblocking).
-    // rbsp is self-cleaning (k_ep_write); stripe flags are cleared by k_plan.
+    // rbsp is self-cleaning (k_ep_write); stripe flags are cleared by k_plan. The overlay
+    // placement is not part of the graph: launch() copies it ahead of the graph when it changed.
     void enqueue(int part) {
         if (part == 0) {
-            // this frame's overlay placement (host copy written at launch()) -> device
-            HIPCHECK(hipMemcpyAsync(ov_params_dev_, ov_params_host_[parity_], sizeof(OverlayParams) * kOverlaySlots,
-                                    hipMemcpyHostToDevice, stream_));
             gpu::launch_convert_damage(args_, stream_);
             if (cfg_.codec == 2) {
                 gpu::launch_frontend(args_, stream_);
@@ -1048,7 +1057,13 @@ class HipBackend : public EncoderBackend {
     hipGraphExec_t graph_exec_[2] = {nullptr, nullptr};
     uint8_t* ov_img_dev_[kOverlaySlots] = {};
     OverlayParams* ov_params_dev_ = nullptr;
-    OverlayParams* ov_params_host_[2] = {};   // per launch parity: copied into the graph
+    // Pinned staging of the placement copies, rotating: launch(n + 2) comes after
+    // finish(n), so the copy queued ahead of graph n has run when its slot is written again.
+    static constexpr int kOvStage = 2;
+    OverlayParams* ov_params_host_[kOvStage] = {};
+    OverlayParams ov_sent_[kOverlaySlots] = {};   // what the device holds
+    int ov_slot_ = 0;
+    bool ov_resend_ = true;                       // first launch, and after a re-capture
     OverlayParams ov_pending_[kOverlaySlots];
     uint8_t* ov_stage_ = nullptr;
     hipGraphExec_t post_exec_[2] = {nullptr, nullptr};
