@@ -63,24 +63,26 @@ void Controller::commit(const SliceTask* tasks) {
         commit_picture(pic_, picture_is_idr(tasks), plan_config(cfg_).num_refs);
         return;
     }
-    for (int s = 0; s < g_.num_slices; s++) commit_stripe(st_[s], tasks[s].final_action, plan_config(cfg_).num_refs);
+    for (int s = 0; s < g_.num_slices; s++)
+        commit_stripe(st_[s], tasks[s].final_action, plan_config(cfg_).num_refs, tasks[s].idr_on_intra != 0);
 }
 
 // ---------------------------------------------------------------------------
-int choose_level_idc(int mb_w, int mb_h, float fps) {
-    struct L { int idc, max_fs, max_mbps; };
-    static const L levels[] = {{10, 99, 1485},       {11, 396, 3000},     {12, 396, 6000},
-                               {13, 396, 11880},     {20, 396, 11880},    {21, 792, 19800},
-                               {22, 1620, 20250},    {30, 1620, 40500},   {31, 3600, 108000},
-                               {32, 5120, 216000},   {40, 8192, 245760},  {42, 8704, 522240},
-                               {50, 22080, 589824},  {51, 36864, 983040}, {52, 36864, 2073600}};
+int choose_level_idc(int mb_w, int mb_h, float fps, int dpb_frames) {
+    struct L { int idc, max_fs, max_mbps, max_dpb_mbs; };   // Table A-1
+    static const L levels[] = {{10, 99, 1485, 396},          {11, 396, 3000, 900},        {12, 396, 6000, 2376},
+                               {13, 396, 11880, 2376},       {20, 396, 11880, 2376},      {21, 792, 19800, 4752},
+                               {22, 1620, 20250, 8100},      {30, 1620, 40500, 8100},     {31, 3600, 108000, 18000},
+                               {32, 5120, 216000, 20480},    {40, 8192, 245760, 32768},   {42, 8704, 522240, 34816},
+                               {50, 22080, 589824, 110400},  {51, 36864, 983040, 184320}, {52, 36864, 2073600, 184320}};
     int fs = mb_w * mb_h;
     long mbps = (long)(fs * (fps > 0 ? fps : 60.f));
     int dim = mb_w > mb_h ? mb_w : mb_h;
     for (const L& l : levels) {
         int maxdim = 1;
         while ((maxdim + 1) * (maxdim + 1) <= 8 * l.max_fs) maxdim++;
-        if (fs <= l.max_fs && mbps <= l.max_mbps && dim <= maxdim) return l.idc;
+        // dpb_frames (long-term cache on): MaxDpbMbs must hold that many frames (A.3.1 h)
+        if (fs <= l.max_fs && mbps <= l.max_mbps && dim <= maxdim && (long)dpb_frames * fs <= l.max_dpb_mbs) return l.idc;
     }
     return 52;
 }
@@ -115,18 +117,20 @@ static void rbsp_trailing(BitWriter& w) {
 }
 
 void build_parameter_sets(int width, int height, int full_range, float fps,
-                          std::vector<uint8_t>& out, int num_refs) {
+                          std::vector<uint8_t>& out, int num_refs, int ltr_slots) {
+    // long-term cache: the DPB holds the short-term picture and every slot
+    const int max_refs = ltr_slots > 0 ? 1 + ltr_slots : (num_refs > 1 ? 2 : 1);
     int mb_w = (width + 15) / 16, mb_h = (height + 15) / 16;
     uint8_t buf[128];
     memset(buf, 0, sizeof(buf));
     BitWriter w(buf);
     w.put(66, 8);          // profile_idc: Baseline
     w.put(0xC0, 8);        // constraint_set0/1 = 1 (Constrained Baseline), reserved 0
-    w.put((uint32_t)choose_level_idc(mb_w, mb_h, fps), 8);
+    w.put((uint32_t)choose_level_idc(mb_w, mb_h, fps, ltr_slots > 0 ? max_refs : 0), 8);
     put_ue(w, 0);          // seq_parameter_set_id
     put_ue(w, kLog2MaxFrameNum - 4);
     put_ue(w, 2);          // pic_order_cnt_type
-    put_ue(w, (uint32_t)(num_refs > 1 ? 2 : 1));   // max_num_ref_frames (sliding window)
+    put_ue(w, (uint32_t)max_refs);   // max_num_ref_frames (sliding window; + the long-term slots)
     w.put(0, 1);           // gaps_in_frame_num_value_allowed_flag
     put_ue(w, (uint32_t)(mb_w - 1));
     put_ue(w, (uint32_t)(mb_h - 1));
@@ -164,7 +168,7 @@ void build_parameter_sets(int width, int height, int full_range, float fps,
     put_ue(w, 11);         // log2_max_mv_length_horizontal
     put_ue(w, 11);         // log2_max_mv_length_vertical
     put_ue(w, 0);          // max_num_reorder_frames
-    put_ue(w, 1);          // max_dec_frame_buffering
+    put_ue(w, (uint32_t)(ltr_slots > 0 ? max_refs : 1));   // max_dec_frame_buffering
     rbsp_trailing(w);
     append_nal(out, 0x67, buf, w.pos / 8);
 

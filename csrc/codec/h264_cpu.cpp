@@ -36,13 +36,26 @@ CpuH264Encoder::CpuH264Encoder(const EncoderConfig& c) : cfg(c) {
     dbinfo.assign(g.num_mbs(), DbInfo());
     fs_mv.assign((size_t)g.num_mbs() * 2, 0);
     tasks.assign(g.num_slices, SliceTask());
+    ltr_slots_ = ltr_slots_of(cfg);
+    if (ltr_slots_) {
+        for (int j = 0; j < ltr_slots_; j++)
+            for (int p = 0; p < 3; p++) ltr_planes[j][p].assign(p ? nc : ny, 0);
+        ltr::LtrState z;
+        ltr::ltr_state_reset(z);
+        ltr_state.assign(g.num_slices + 1, z);
+        ltr::LtrTask zt;
+        ltr::ltr_task_reset(zt);
+        ltr_task.assign(g.num_slices, zt);
+        ltr_sad.assign((size_t)g.num_slices * ltr::kLtrSadCols, 0);
+    }
     if (cfg.fullframe) {
         param_sets.resize(1);
-        build_parameter_sets(g.W, g.H, cfg.full_range, cfg.fps, param_sets[0], cfg.num_refs);
+        build_parameter_sets(g.W, g.H, cfg.full_range, cfg.fps, param_sets[0], cfg.num_refs, ltr_slots_);
     } else {
         param_sets.resize(g.num_slices);
         for (int s = 0; s < g.num_slices; s++)
-            build_parameter_sets(g.W, g.slice_pix_h(s), cfg.full_range, cfg.fps, param_sets[s], cfg.num_refs);
+            build_parameter_sets(g.W, g.slice_pix_h(s), cfg.full_range, cfg.fps, param_sets[s], cfg.num_refs,
+                                 ltr_slots_);
     }
 }
 
@@ -158,7 +171,7 @@ int CpuH264Encoder::sad_at(int mbx, int mby, int dx, int dy, const SliceTask& t,
     for (int y = 0; y < 16; y++) {
         int sy = sk_clip(mby * 16 + y + dy, y_lo, y_hi);
         const uint8_t* s = &src[0][(size_t)(mby * 16 + y) * g.stride_y + mbx * 16];
-        const uint8_t* r = &refs(refi)[0][(size_t)sy * g.stride_y];
+        const uint8_t* r = &refs(refi, t)[0][(size_t)sy * g.stride_y];
         for (int x = 0; x < 16; x++) {
             int sx = sk_clip(mbx * 16 + x + dx, 0, x_hi);
             sad += sk_abs((int)s[x] - (int)r[sx]);
@@ -315,7 +328,7 @@ void CpuH264Encoder::subpel_refine(int s) {
             MeResult& r = me[(size_t)mby * g.mb_w + mbx];
             r.fx = r.fy = 0;
             if (r.sad <= kSubpelMinSad) continue;
-            const uint8_t* ref = refs(r.ref)[0].data();
+            const uint8_t* ref = refs(r.ref, t)[0].data();
             auto sad_q = [&](int qx, int qy) {
                 int sad = 0;
                 for (int y = 0; y < 16; y++) {
@@ -349,20 +362,63 @@ void CpuH264Encoder::subpel_refine(int s) {
 void CpuH264Encoder::decide_scenecut(int s) {
     SliceTask& t = tasks[s];
     t.final_action = t.action;
-    if (t.action != ACT_P || !t.allow_scenecut) return;
+    if (t.action != ACT_P) return;
     long long inter = 0, intra = 0;
+    int ref1 = 0;
     for (int mby = t.first_row; mby < t.first_row + t.num_rows; mby++)
         for (int mbx = 0; mbx < g.mb_w; mbx++) {
             inter += me[mby * g.mb_w + mbx].sad;
             intra += me[mby * g.mb_w + mbx].intra_est;
+            ref1 += me[mby * g.mb_w + mbx].ref == 1;
         }
-    if (inter > intra) t.final_action = ACT_I;
+    if (t.allow_scenecut && inter > intra) t.final_action = ACT_I;
+    if (ltr_slots_) ltr_task[s].ref1_mbs = t.final_action == ACT_P ? ref1 : 0;   // the stream's cur_slot (ltr_commit)
+}
+
+// Long-term cache, once per frame between planning and motion search (k_ltr_match +
+// k_ltr_decide): dirty count of every stream, on a gated frame the zero-vector luma SADs
+// of its slices against the current reference and every valid slot, then ltr_decide.
+void CpuH264Encoder::ltr_plan() {
+    const int ns = g.num_slices;
+    auto decide = [&](ltr::LtrState& st, int s0, int s1) {
+        const int r0 = tasks[s0].first_row, r1 = tasks[s1 - 1].first_row + tasks[s1 - 1].num_rows;
+        const int n = (r1 - r0) * g.mb_w;
+        int nd = 0;
+        for (int j = r0 * g.mb_w; j < r1 * g.mb_w; j++) nd += mb_dirty[j] != 0;
+        bool planned_p = false, key = false;
+        for (int s = s0; s < s1; s++) {
+            planned_p |= tasks[s].action == ACT_P;
+            key |= tasks[s].action == ACT_I;
+        }
+        planned_p = planned_p && !key;
+        if (planned_p && ltr::ltr_large(nd, n) && st.valid)
+            for (int s = s0; s < s1; s++) {
+                if (tasks[s].action != ACT_P) continue;
+                const size_t o0 = (size_t)tasks[s].first_row * 16 * g.stride_y;
+                const size_t cnt = (size_t)tasks[s].num_rows * 16 * g.stride_y;
+                for (int c = 0; c < 1 + ltr_slots_; c++) {
+                    if (c > 0 && !((st.valid >> (c - 1)) & 1)) continue;
+                    const uint8_t* r = (c ? ltr_planes[c - 1][0] : ref[0]).data() + o0;
+                    const uint8_t* q = src[0].data() + o0;
+                    uint32_t sum = 0;
+                    for (size_t i = 0; i < cnt; i++) sum += (uint32_t)sk_abs((int)q[i] - (int)r[i]);
+                    ltr_sad[(size_t)s * ltr::kLtrSadCols + c] = sum;
+                }
+            }
+        ltr::ltr_decide(ltr_slots_, st, nd, n, planned_p, tasks[s0].frame_num, kFrameNumMask, s0, s1,
+                        [&](int s) { return tasks[s].action == ACT_P; }, ltr_sad.data(), ltr_task.data());
+        for (int s = s0; s < s1; s++)
+            if (ltr_task[s].slot >= 0) tasks[s].num_refs = 2;   // [previous picture, the slot]
+    };
+    if (cfg.fullframe) decide(ltr_state[ns], 0, ns);
+    else
+        for (int s = 0; s < ns; s++) decide(ltr_state[s], s, s + 1);
 }
 
 void CpuH264Encoder::mc_luma(int mbx, int mby, int mvx, int mvy, const SliceTask& t,
                              uint8_t* pred, int refi) const {
     int y_lo = t.pic_row0 * 16, y_hi = (t.pic_row0 + t.pic_rows) * 16 - 1;
-    const uint8_t* ref = refs(refi)[0].data();
+    const uint8_t* ref = refs(refi, t)[0].data();
     for (int y = 0; y < 16; y++)
         for (int x = 0; x < 16; x++)
             pred[y * 16 + x] = (uint8_t)luma_qpel_sample(ref, g.stride_y, g.stride_y, y_lo, y_hi, mbx * 16 + x,
@@ -374,7 +430,7 @@ void CpuH264Encoder::mc_chroma(int mbx, int mby, int mvx, int mvy, const SliceTa
     int h = t.pic_rows * 8;
     int y0 = t.pic_row0 * 8;
     for (int c = 0; c < 2; c++) {
-        const uint8_t* base = &refs(refi)[1 + c][(size_t)y0 * g.stride_c];
+        const uint8_t* base = &refs(refi, t)[1 + c][(size_t)y0 * g.stride_c];
         uint8_t* o = c ? pv : pu;
         for (int y = 0; y < 8; y++)
             for (int x = 0; x < 8; x++)
@@ -716,6 +772,15 @@ std::vector<std::vector<uint8_t>> CpuH264Encoder::write_slice(int s) {
         h.slice_qp = t.qp;
         h.deblock = slice_deblock(cfg.deblock, t);
         h.num_refs = intra ? 1 : t.num_refs;
+        if (ltr_slots_) {
+            const ltr::LtrTask& L = ltr_task[s];
+            if (t.final_action == ACT_P) h.lt_ref = L.slot;
+            if (!h.idr && L.store_slot >= 0) {   // every slice NAL of the picture carries the same marking
+                h.lt_store = L.store_slot;
+                h.lt_max_idx = ltr_slots_;
+                h.st_drop = L.mmco1;
+            }
+        }
         write_slice_header(w, h);
         if (t.final_action == ACT_SKIPALL) {
             put_ue(w, (uint32_t)nmb);
@@ -763,7 +828,7 @@ void CpuH264Encoder::package(uint16_t frame_id, std::vector<std::vector<std::vec
     for (int s = 0; s < g.num_slices; s++) {
         const SliceTask& t = tasks[s];
         if (t.final_action == ACT_NONE) continue;
-        bool idr = t.final_action == ACT_I;
+        bool idr = t.final_action == ACT_I && t.idr_on_intra;   // non-IDR I: long-term cache on, scene cut
         EncodedPacket pk;
         pk.y = g.slice_pix_y(s); pk.w = g.W; pk.h = g.slice_pix_h(s); pk.key = idr;
         pk.data.resize(10);
@@ -778,6 +843,14 @@ void CpuH264Encoder::finish_frame() {
     for (int s = 0; s < g.num_slices; s++) {
         const SliceTask& t = tasks[s];
         const int y0 = t.first_row * 16, y1 = (t.first_row + t.num_rows) * 16;
+        if (ltr_slots_ && ltr_task[s].store_slot >= 0) {
+            // long-term store: the previous picture's rows, before the new reconstruction replaces them
+            std::vector<uint8_t>* slot = ltr_planes[ltr_task[s].store_slot];
+            memcpy(&slot[0][(size_t)y0 * g.stride_y], &ref[0][(size_t)y0 * g.stride_y], (size_t)(y1 - y0) * g.stride_y);
+            for (int p = 1; p < 3; p++)
+                memcpy(&slot[p][(size_t)(y0 / 2) * g.stride_c], &ref[p][(size_t)(y0 / 2) * g.stride_c],
+                       (size_t)(y1 - y0) / 2 * g.stride_c);
+        }
         if (cfg.num_refs > 1 && t.final_action != ACT_NONE) {
             // sliding window: the picture before the one being added becomes reference 1
             // (a skip-all picture is a reference too: ref 1 = the old ref 0 = its content)
@@ -813,6 +886,18 @@ void CpuH264Encoder::finish_frame() {
             }
     }
     for (int p = 0; p < 3; p++) prev[p].swap(src[p]);
+    if (ltr_slots_) {
+        const int ns = g.num_slices;
+        if (cfg.fullframe) {
+            ltr::ltr_commit(ltr_slots_, ltr_state[ns], true, ctl_.picture_is_idr(tasks.data()), tasks[0].frame_num,
+                            g.num_mbs(), 0, ns, ltr_task.data());
+        } else {
+            for (int s = 0; s < ns; s++)
+                ltr::ltr_commit(ltr_slots_, ltr_state[s], tasks[s].final_action != ACT_NONE,
+                                tasks[s].final_action == ACT_I && tasks[s].idr_on_intra, tasks[s].frame_num,
+                                tasks[s].num_rows * g.mb_w, s, s + 1, ltr_task.data());
+        }
+    }
     ctl_.commit(tasks.data());
     first_frame = false;
 }
@@ -844,6 +929,7 @@ void CpuH264Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id,
         st.subpel_prev = st.subpel_hits;
         st.subpel_hits = 0;
     }
+    if (ltr_slots_) ltr_plan();
     for (int s = 0; s < g.num_slices; s++)
         if (tasks[s].action == ACT_P) {
             motion_search(s);

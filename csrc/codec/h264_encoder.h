@@ -16,6 +16,7 @@
 #include <string>
 #include "h264_core.h"
 #include "ratecontrol.h"
+#include "ltr.h"
 
 namespace sk {
 namespace h264 {
@@ -56,7 +57,28 @@ struct EncoderConfig {
     int subpel = 1;              // quarter-pel refinement of P vectors (K4c, H.264 and HEVC); AV1 keeps integer vectors
     int intra4x4 = 0;            // H.264 I slices may code MBs as I_NxN (nine 4x4 modes) where cheaper; off
                                  // by default like x264's ultrafast preset (partitions none)
+    int ltr_slots = 0;           // H.264 long-term reference cache (ltr.h): pictures kept per stream for content
+                                 // that comes back (window switches); 0 = off, 1..8; excludes num_refs > 1
 };
+
+// Long-term cache slots in force: H.264 only (HEVC / AV1 share this configuration and the front end).
+inline int ltr_slots_of(const EncoderConfig& c) {
+    return c.codec == 0 && c.ltr_slots > 0 ? (c.ltr_slots < ltr::kLtrMaxSlots ? c.ltr_slots : ltr::kLtrMaxSlots) : 0;
+}
+
+// Why a configuration cannot run the long-term cache (nullptr: it can, or the cache is off).
+inline const char* ltr_config_error(const EncoderConfig& c) {
+    if (c.codec != 0 || c.ltr_slots <= 0) return nullptr;
+    if (c.ltr_slots > ltr::kLtrMaxSlots) return "ltr_slots must be 0 (off) or 1..8";
+    if (c.num_refs > 1)
+        return "ltr_slots > 0 cannot be combined with num_refs > 1: the cached picture takes the second reference "
+               "list position";
+    // the largest stream's DPB (one short-term picture + the slots) must fit level 5.2 (Table A-1 MaxDpbMbs)
+    const int sh = c.fullframe ? c.height : (c.height < c.stripe_height ? c.height : c.stripe_height);
+    if ((long)(1 + c.ltr_slots) * ((c.width + 15) / 16) * ((sh + 15) / 16) > 184320)
+        return "ltr_slots: the decoded picture buffer would exceed H.264 level 5.2 (MaxDpbMbs)";
+    return nullptr;
+}
 
 struct Geometry {
     int W = 0, H = 0, mb_w = 0, mb_h = 0, rows_per_slice = 0, num_slices = 0;
@@ -168,11 +190,12 @@ struct StripeState {
 struct PlanConfig {
     int32_t fullframe, scenecut, use_paint_over, paint_over_trigger, paint_over_burst;
     int32_t damage_threshold, damage_duration, streaming_mode, qp, paint_qp, num_refs;
+    int32_t ltr_slots;   // > 0: a stripe's scene-cut I slice stays a non-IDR picture (the cache survives it)
 };
 inline PlanConfig plan_config(const EncoderConfig& c) {
     return PlanConfig{c.fullframe, c.scenecut, c.use_paint_over, c.paint_over_trigger, c.paint_over_burst,
                       c.damage_threshold, c.damage_duration, c.streaming_mode, c.qp, c.paint_qp,
-                      c.num_refs > 1 ? 2 : 1};
+                      c.num_refs > 1 ? 2 : 1, ltr_slots_of(c)};
 }
 constexpr int kFrameNumMask = (1 << 16) - 1;  // log2_max_frame_num = 16 (h264_syntax.h)
 
@@ -186,7 +209,7 @@ SK_HD void plan_stripe(const PlanConfig& c, StripeState& st, const StripeState& 
     t.pic_row0 = ff ? 0 : first_row;
     t.pic_rows = ff ? mb_h : num_rows;
     t.allow_scenecut = c.scenecut;
-    t.idr_on_intra = ff ? 0 : 1;
+    t.idr_on_intra = (ff || c.ltr_slots > 0) ? 0 : 1;
     if (d) {
         st.static_frames = 0;
         st.dirty_streak++;
@@ -224,6 +247,7 @@ SK_HD void plan_stripe(const PlanConfig& c, StripeState& st, const StripeState& 
         t.idr_pic_id = pic.idr_pic_id;
         if (need_idr) t.idr_on_intra = 1;
     } else {
+        if (need_idr) t.idr_on_intra = 1;
         t.frame_num = st.frame_num;
         t.idr_pic_id = st.idr_pic_id;
     }
@@ -233,13 +257,15 @@ SK_HD void plan_stripe(const PlanConfig& c, StripeState& st, const StripeState& 
 }
 
 // Striped mode: stripe state after its slice was coded with `final_action`.
-SK_HD void commit_stripe(StripeState& st, int final_action, int max_refs) {
-    if (final_action == ACT_I) {
+// `idr`: an I slice was an IDR picture (always, unless the long-term cache keeps it a non-IDR I picture,
+// whose frame_num advances as for P).
+SK_HD void commit_stripe(StripeState& st, int final_action, int max_refs, bool idr = true) {
+    if (final_action == ACT_I && idr) {
         st.frame_num = 1;
         st.idr_pic_id = (st.idr_pic_id + 1) & 0xffff;
         st.need_idr = false;
         st.refs = 1;
-    } else if (final_action == ACT_P) {
+    } else if (final_action == ACT_P || final_action == ACT_I) {
         st.frame_num = (st.frame_num + 1) & kFrameNumMask;
         st.refs = st.refs + 1 < max_refs ? st.refs + 1 : max_refs;
     }
@@ -389,14 +415,17 @@ class Controller {
 //   frame_num is also the next HEVC POC) | RcState (K10) | ref | ref1 | last source
 //   (4:2:0 planes) | MV field. The reference planes are what the next frame predicts from
 //   (HEVC: after deblocking + SAO, AV1: after loop filter + CDEF).
+// With the H.264 long-term cache on (ltr_slots > 0) the blob is version 4: the version-3 layout, then
+//   LtrState[num_slices + 1] | slot 0 Y U V | slot 1 Y U V | ...  Without it the blob stays version 3.
 struct StateHeader {
     char magic[4];          // "SKH4"
-    int32_t version;        // 3 (codec, RcState)
+    int32_t version;        // 3 (codec, RcState); 4 = 3 + long-term cache (EncoderConfig::ltr_slots > 0)
     int32_t W, H, stripe_height, fullframe, num_slices;
     int32_t started;        // a frame has been encoded (else the next one is all-dirty)
     int32_t qp, paint_qp;   // rate-control QPs in force
     int32_t codec;          // EncoderConfig::codec
-    int32_t reserved[5];
+    int32_t ltr_slots;      // version 4: slot plane sets that follow (0 in version 3, where the word was reserved)
+    int32_t reserved[4];
 };
 static_assert(sizeof(StateHeader) == 64, "StateHeader layout");
 
@@ -406,14 +435,20 @@ inline size_t state_plane_bytes(const Geometry& g) {
 inline size_t state_head_bytes(const Geometry& g) {   // header + controller + rate control
     return sizeof(StateHeader) + sizeof(StripeState) * (size_t)(g.num_slices + 1) + sizeof(RcState);
 }
-inline size_t state_bytes(const Geometry& g) {
-    return state_head_bytes(g) + 3 * state_plane_bytes(g) + sizeof(int16_t) * 2 * (size_t)g.num_mbs();
+// Version 4 appends LtrState[num_slices + 1] (last = the picture's, full-frame mode) and the slot plane sets.
+inline size_t state_ltr_bytes(const Geometry& g, int ltr_slots) {
+    return ltr_slots > 0 ? sizeof(ltr::LtrState) * (size_t)(g.num_slices + 1) + (size_t)ltr_slots * state_plane_bytes(g) : 0;
+}
+inline size_t state_bytes(const Geometry& g, int ltr_slots = 0) {
+    return state_head_bytes(g) + 3 * state_plane_bytes(g) + sizeof(int16_t) * 2 * (size_t)g.num_mbs() +
+           state_ltr_bytes(g, ltr_slots);
 }
 inline void state_header(const EncoderConfig& c, const Geometry& g, int started, int qp, int paint_qp,
                          StateHeader& h) {
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "SKH4", 4);
-    h.version = 3;
+    h.version = ltr_slots_of(c) > 0 ? 4 : 3;
+    h.ltr_slots = ltr_slots_of(c);
     h.codec = c.codec;
     h.W = g.W;
     h.H = g.H;
@@ -425,15 +460,16 @@ inline void state_header(const EncoderConfig& c, const Geometry& g, int started,
     h.paint_qp = paint_qp;
 }
 inline bool state_header_matches(const EncoderConfig& c, const Geometry& g, const StateHeader& h) {
-    return memcmp(h.magic, "SKH4", 4) == 0 && h.version == 3 && h.codec == c.codec && h.W == g.W && h.H == g.H &&
+    return memcmp(h.magic, "SKH4", 4) == 0 && h.version == (ltr_slots_of(c) > 0 ? 4 : 3) &&
+           h.ltr_slots == ltr_slots_of(c) && h.codec == c.codec && h.W == g.W && h.H == g.H &&
            h.stripe_height == c.stripe_height && h.fullframe == c.fullframe && h.num_slices == g.num_slices;
 }
 
 // ---- bitstream packaging (host) -------------------------------------------
-int choose_level_idc(int mb_w, int mb_h, float fps);
+int choose_level_idc(int mb_w, int mb_h, float fps, int dpb_frames = 0);
 // SPS + PPS NAL units (Annex-B, with start codes) for a picture of w x h pixels.
 void build_parameter_sets(int width, int height, int full_range, float fps,
-                          std::vector<uint8_t>& out, int num_refs = 1);
+                          std::vector<uint8_t>& out, int num_refs = 1, int ltr_slots = 0);
 // Appends start code + NAL header + EP-escaped payload.
 void append_nal(std::vector<uint8_t>& out, int nal_header_byte, const uint8_t* rbsp, size_t n);
 size_t emulation_prevent(const uint8_t* in, size_t n, uint8_t* out);

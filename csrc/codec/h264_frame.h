@@ -83,6 +83,7 @@ class CpuH264Encoder {
     int mb_activity(int mbx, int mby) const;
     void subpel_refine(int s);                              // K4c: half + quarter-pel refinement
     void decide_scenecut(int s);
+    void ltr_plan();                                        // long-term cache decisions (ltr.h), after planning
     void compute_aq(int s);                                 // AQ offsets of slice s's MBs
     int mb_start_qp(const SliceTask& t, int idx) const {
         return cfg.aq_strength > 0 ? aq_start_qp(t.qp, aq[idx]) : -1;
@@ -100,6 +101,13 @@ class CpuH264Encoder {
     Controller ctl_;
     std::vector<uint8_t> src[3], prev[3], ref[3], rec[3];
     std::vector<uint8_t> ref1[3];  // second reference (previous-but-one picture) when num_refs == 2
+    // Long-term reference cache (cfg.ltr_slots, ltr.h): plane sets (a stripe's slot j lives at the stripe's
+    // rows of set j), the per-stream state ([num_slices] stripes, then the picture's) and the per-slice decisions
+    int ltr_slots_ = 0;
+    std::vector<uint8_t> ltr_planes[ltr::kLtrMaxSlots][3];
+    std::vector<ltr::LtrState> ltr_state;
+    std::vector<ltr::LtrTask> ltr_task;
+    std::vector<uint32_t> ltr_sad;   // [num_slices][kLtrSadCols] zero-vector luma SADs of a gated frame
     std::vector<uint8_t> mb_dirty, stripe_dirty;
     std::vector<MbInfo> mbs;
     std::vector<int16_t> coefs;
@@ -132,7 +140,11 @@ class CpuH264Encoder {
     void mc_chroma(int mbx, int mby, int mvx, int mvy, const SliceTask& t, uint8_t* pu,
                    uint8_t* pv, int refi = 0) const;
     int sad_at(int mbx, int mby, int dx, int dy, const SliceTask& t, int refi = 0) const;
-    const std::vector<uint8_t>* refs(int refi) const { return refi ? ref1 : ref; }
+    // reference index 1 of slice t: the slice's cached picture (long-term cache), else the previous-but-one
+    const std::vector<uint8_t>* refs(int refi, const SliceTask& t) const {
+        if (!refi) return ref;
+        return ltr_slots_ ? ltr_planes[sk_max(ltr_task[t.first_row / g.rows_per_slice].slot, 0)] : ref1;
+    }
     void full_search(int mbx, int mby, const SliceTask& t, int16_t* out) const;
 };
 

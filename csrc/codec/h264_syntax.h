@@ -18,6 +18,11 @@ struct SliceHeaderParams {
     int slice_qp;
     int deblock;      // 1: filter inside the slice (idc 2), 0: filter off (idc 1)
     int num_refs;     // P: active references (> 1 overrides the PPS default of 1)
+    // Long-term references (ltr.h); at these defaults the header is the sliding-window one.
+    int lt_ref = -1;        // P: list 0 becomes [previous picture, LongTermPicNum lt_ref] (two active references)
+    int lt_store = -1;      // the previous picture becomes long-term frame index lt_store (MMCO 3)
+    int lt_max_idx = 0;     // with lt_store: max_long_term_frame_idx_plus1 (MMCO 4)
+    int st_drop = -1;       // with lt_store: difference_of_pic_nums_minus1 of a short-term picture to drop (MMCO 1)
 };
 
 template <class W>
@@ -29,18 +34,41 @@ SK_HD void write_slice_header(W& w, const SliceHeaderParams& h) {
     if (h.idr) put_ue(w, (uint32_t)h.idr_pic_id);
     // pic_order_cnt_type == 2: no POC syntax
     if (h.slice_type == 0) {
-        if (h.num_refs > 1) {
+        if (h.lt_ref >= 0) {
             w.put(1, 1);  // num_ref_idx_active_override_flag
-            put_ue(w, (uint32_t)(h.num_refs - 1));
+            put_ue(w, 1);  // two references
+            w.put(1, 1);  // ref_pic_list_modification_flag_l0 (7.3.3.1, 8.2.4.3)
+            put_ue(w, 0);  // modification_of_pic_nums_idc 0: subtract
+            put_ue(w, 0);  //   abs_diff_pic_num_minus1 = 0: the previous picture at index 0
+            put_ue(w, 2);  // modification_of_pic_nums_idc 2: long-term picture at index 1
+            put_ue(w, (uint32_t)h.lt_ref);  //   long_term_pic_num
+            put_ue(w, 3);  // end of the list
         } else {
-            w.put(0, 1);
+            if (h.num_refs > 1) {
+                w.put(1, 1);  // num_ref_idx_active_override_flag
+                put_ue(w, (uint32_t)(h.num_refs - 1));
+            } else {
+                w.put(0, 1);
+            }
+            w.put(0, 1);  // ref_pic_list_modification_flag_l0 (default order: most recent first)
         }
-        w.put(0, 1);  // ref_pic_list_modification_flag_l0 (default order: most recent first)
     }
     // dec_ref_pic_marking() (nal_ref_idc != 0)
     if (h.idr) {
         w.put(0, 1);  // no_output_of_prior_pics_flag
         w.put(0, 1);  // long_term_reference_flag
+    } else if (h.lt_store >= 0) {
+        w.put(1, 1);  // adaptive_ref_pic_marking_mode_flag (7.3.3.3, 8.2.5.4)
+        put_ue(w, 4);  // MMCO 4: long-term frame indices 0 .. lt_max_idx - 1
+        put_ue(w, (uint32_t)h.lt_max_idx);
+        if (h.st_drop >= 0) {
+            put_ue(w, 1);  // MMCO 1: a short-term picture leaves, so the DPB keeps its bound
+            put_ue(w, (uint32_t)h.st_drop);
+        }
+        put_ue(w, 3);  // MMCO 3: the previous picture (difference_of_pic_nums_minus1 = 0) turns long-term
+        put_ue(w, 0);
+        put_ue(w, (uint32_t)h.lt_store);
+        put_ue(w, 0);  // MMCO 0: end
     } else {
         w.put(0, 1);  // adaptive_ref_pic_marking_mode_flag
     }

@@ -1,0 +1,187 @@
+// Long-term reference cache: the policy that decides which reconstructed pictures a
+// stream keeps beyond its sliding window, when a slice predicts from one of them, and
+// the model of the decoder's reference marking that keeps the stream inside its DPB.
+// POD state and SK_HD functions only, codec-agnostic (frame numbers are the codec's
+// picture counter modulo `fn_mask + 1`), so the CPU back end and the GPU frame graph run
+// the same code and a later codec can reuse it.
+//
+// A stream is what owns a decoder: a stripe in striped mode, the picture in full-frame
+// mode. All quantities are integers, so both back ends decide identically.
+#pragma once
+#include <stdint.h>
+#include "sk_common.h"
+
+namespace sk {
+namespace ltr {
+
+constexpr int kLtrMaxSlots = 8;    // EncoderConfig::ltr_slots upper bound
+constexpr int kLtrSettle = 8;      // consecutive quiet frames after which a stream's content counts as settled
+constexpr int kLtrQuietDen = 16;   // quiet frame: dirty MBs < 1/16 of the stream's MBs
+constexpr int kLtrLargeDen = 4;    // large change: dirty MBs >= 1/4 of the stream's MBs
+constexpr int kLtrSadCols = 1 + kLtrMaxSlots;   // per slice: SAD against the current reference, then each slot
+
+// Per stream, carried from frame to frame (and in the version-4 state blob).
+struct LtrState {
+    int32_t quiet_run;             // consecutive quiet frames up to now
+    int32_t cur_slot;              // slot that holds the stream's current content, -1: none
+    int32_t clock;                 // frames with a large change seen (the stamps' time base)
+    int32_t valid;                 // bit j: slot j holds a picture == long-term frame index j in use
+    int32_t stamp[kLtrMaxSlots];   // clock of the slot's last store or match
+    // model of the decoder's marking state (8.2.5): short-term frame_nums, oldest first
+    int32_t n_st;
+    int32_t st_fn[kLtrMaxSlots + 1];
+    int32_t pad[2];
+};
+static_assert(sizeof(LtrState) == 96, "LtrState layout");
+
+enum LtrFlags : int32_t { LTR_GATED = 1, LTR_DRIFT = 2 };
+
+// Per slice and frame: what the policy decided (parallel to SliceTask).
+struct LtrTask {
+    int32_t slot;         // cached picture this slice predicts from (reference index 1), -1: none
+    int32_t store_slot;   // the stream's previous picture becomes long-term index store_slot, -1: no store
+    int32_t mmco1;        // difference_of_pic_nums_minus1 of the short-term picture to drop first, -1: none
+    int32_t flags;        // LtrFlags of the stream's frame
+    int32_t ref1_mbs;     // macroblocks of the slice coded from `slot` (set with the scene-cut decision)
+    int32_t pad[3];
+};
+static_assert(sizeof(LtrTask) == 32, "LtrTask layout");
+
+SK_HD void ltr_state_reset(LtrState& st) {
+    st.quiet_run = 0;
+    st.cur_slot = -1;
+    st.clock = 0;
+    st.valid = 0;
+    for (int j = 0; j < kLtrMaxSlots; j++) st.stamp[j] = 0;
+    st.n_st = 0;
+    for (int j = 0; j <= kLtrMaxSlots; j++) st.st_fn[j] = 0;
+    st.pad[0] = st.pad[1] = 0;
+}
+
+SK_HD void ltr_task_reset(LtrTask& t) {
+    t.slot = t.store_slot = t.mmco1 = -1;
+    t.flags = t.ref1_mbs = 0;
+    t.pad[0] = t.pad[1] = t.pad[2] = 0;
+}
+
+SK_HD bool ltr_quiet(int dirty, int mbs) { return dirty * kLtrQuietDen < mbs; }
+SK_HD bool ltr_large(int dirty, int mbs) { return dirty * kLtrLargeDen >= mbs; }
+SK_HD int ltr_popcount(int v) {
+    int n = 0;
+    for (int j = 0; j < kLtrMaxSlots; j++) n += (v >> j) & 1;
+    return n;
+}
+
+// Slot a slice predicts from: the valid slot with the smallest zero-vector SAD if it
+// beats the current reference (ties: lowest index), else -1. sad[0] is the SAD against
+// the current reference, sad[1 + j] against slot j.
+SK_HD int ltr_match(int valid, int slots, const uint32_t* sad) {
+    int best = -1;
+    uint32_t bs = sad[0];
+    for (int j = 0; j < slots; j++)
+        if (((valid >> j) & 1) && sad[1 + j] < bs) {
+            bs = sad[1 + j];
+            best = j;
+        }
+    return best;
+}
+
+// Slot the previous picture is stored into: the lowest free one, else the least
+// recently used (ties: lowest index).
+SK_HD int ltr_store_slot(const LtrState& st, int slots) {
+    for (int j = 0; j < slots; j++)
+        if (!((st.valid >> j) & 1)) return j;
+    int best = 0;
+    for (int j = 1; j < slots; j++)
+        if (st.stamp[j] < st.stamp[best]) best = j;
+    return best;
+}
+
+// The stream's decision for one frame, before motion search. `dirty` of the stream's
+// `mbs` macroblocks changed; `planned_p`: the picture is planned as P (no key frame);
+// slices [s0, s1) belong to the stream and slice s may predict when p_slice(s). `sad`
+// holds kLtrSadCols sums per slice and is only read on a gated frame. Fills lt[s0..s1)
+// and updates the quiet run, the clock and the stamps; the marking model moves in
+// ltr_commit.
+template <class IsP>
+SK_HD void ltr_decide(int slots, LtrState& st, int dirty, int mbs, bool planned_p, int frame_num, int fn_mask,
+                      int s0, int s1, IsP p_slice, const uint32_t* sad, LtrTask* lt) {
+    const bool settled = st.quiet_run >= kLtrSettle;
+    const bool quiet = ltr_quiet(dirty, mbs), large = ltr_large(dirty, mbs);
+    st.quiet_run = quiet ? st.quiet_run + 1 : 0;
+    for (int s = s0; s < s1; s++) ltr_task_reset(lt[s]);
+    int flags = 0;
+    if (large && planned_p) flags = LTR_GATED;
+    else if (!quiet) flags = LTR_DRIFT;
+    int store = -1, mmco1 = -1;
+    if (flags & LTR_GATED) {
+        st.clock++;
+        for (int s = s0; s < s1; s++) {
+            if (!p_slice(s)) continue;
+            const int j = ltr_match(st.valid, slots, sad + (size_t)s * kLtrSadCols);
+            lt[s].slot = j;
+            if (j >= 0) st.stamp[j] = st.clock;
+        }
+        if (st.cur_slot >= 0) {
+            st.stamp[st.cur_slot] = st.clock;
+        } else if (settled && st.n_st > 0) {
+            store = ltr_store_slot(st, slots);
+            st.stamp[store] = st.clock;
+            // DPB after marking: the short-term pictures (the previous one leaves, this one
+            // joins) and the long-term ones; over max_num_ref_frames = 1 + slots the oldest
+            // short-term picture goes first (MMCO 1)
+            const int n_lt = ltr_popcount(st.valid) + (((st.valid >> store) & 1) ? 0 : 1);
+            if (st.n_st + n_lt > 1 + slots && st.n_st >= 2)
+                mmco1 = ((frame_num - st.st_fn[0]) & fn_mask) - 1;
+        }
+    }
+    for (int s = s0; s < s1; s++) {
+        lt[s].store_slot = store;
+        lt[s].mmco1 = mmco1;
+        lt[s].flags = flags;
+    }
+}
+
+// After the stream's picture was coded (`coded`: it produced a picture at all; `idr`: an
+// IDR picture): current-content slot from the per-slice reference counts, then the
+// marking model follows what the decoder does with the picture's dec_ref_pic_marking().
+SK_HD void ltr_commit(int slots, LtrState& st, bool coded, bool idr, int frame_num, int mbs, int s0, int s1,
+                      const LtrTask* lt) {
+    if (!coded) return;
+    if (idr) {   // an IDR empties the DPB: no long-term pictures, one short-term (frame_num 0)
+        const int q = st.quiet_run;
+        ltr_state_reset(st);
+        st.quiet_run = q;
+        st.n_st = 1;
+        st.st_fn[0] = 0;
+        return;
+    }
+    const LtrTask& f = lt[s0];
+    if (f.flags & LTR_GATED) {
+        st.cur_slot = -1;
+        for (int j = slots - 1; j >= 0; j--) {
+            int cnt = 0;
+            for (int s = s0; s < s1; s++)
+                if (lt[s].slot == j) cnt += lt[s].ref1_mbs;
+            if (2 * cnt >= mbs) st.cur_slot = j;
+        }
+        if (st.cur_slot >= 0 && st.cur_slot == f.store_slot) st.cur_slot = -1;   // the slot now holds the previous content
+    } else if (f.flags & LTR_DRIFT) {
+        st.cur_slot = -1;   // neither quiet nor a switch: the content moved away from the slot's
+    }
+    if (f.store_slot >= 0) {
+        if (f.mmco1 >= 0) {   // MMCO 1: the oldest short-term picture
+            for (int k = 1; k < st.n_st; k++) st.st_fn[k - 1] = st.st_fn[k];
+            st.n_st--;
+        }
+        st.n_st--;            // MMCO 3: the previous picture (the newest short-term one) turns long-term
+        st.valid |= 1 << f.store_slot;
+    } else if (st.n_st + ltr_popcount(st.valid) >= 1 + slots && st.n_st > 0) {
+        for (int k = 1; k < st.n_st; k++) st.st_fn[k - 1] = st.st_fn[k];   // sliding window (8.2.5.3)
+        st.n_st--;
+    }
+    st.st_fn[st.n_st++] = frame_num;
+}
+
+}  // namespace ltr
+}  // namespace sk

@@ -88,6 +88,16 @@ struct FrameArgs {
     // 2 * ((W+1)/2)); yuv_fmt 0: BGRx input through k_convert_damage
     const uint8_t* yuv;
     int yuv_fmt;
+    // Long-term reference cache (codec/ltr.h), ltr_slots > 0: H.264 only. Slot j's planes lie at
+    // ltr.y + j * ltr_ny and ltr.u / ltr.v + j * ltr_nc (a stripe's slot at the stripe's rows).
+    int ltr_slots;
+    Planes ltr;
+    size_t ltr_ny, ltr_nc;
+    ltr::LtrState* ltr_state;   // [num_slices + 1] per stream (last = the picture's, full-frame mode)
+    ltr::LtrTask* ltr_task;     // [num_slices] this frame's decisions
+    uint32_t* ltr_part;         // [num_slices][kLtrSadCols][rows_per_slice] zero-vector SADs per MB row (k_ltr_match)
+    uint32_t* ltr_sad;          // [num_slices][kLtrSadCols] their sums (k_ltr_decide)
+    int* ltr_cnt;               // [num_slices][2] the slice's stream: dirty MBs, SADs computed (gated frame)
 };
 
 // K1 + K3, or k_yuv_damage for planar input. Also fetches the frame's host-mapped words

@@ -54,6 +54,14 @@ __device__ __forceinline__ int wave_sum(int v) {
            __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
 }
 
+// Reference index 1 of slice s: the cached picture the slice chose (long-term cache, ltr.h),
+// else the previous-but-one picture.
+__device__ __forceinline__ Planes ref1_planes(const FrameArgs& a, int s) {
+    if (!a.ltr_slots) return a.ref1;
+    const size_t j = (size_t)sk_max(a.ltr_task[s].slot, 0);
+    return Planes{a.ltr.y + j * a.ltr_ny, a.ltr.u + j * a.ltr_nc, a.ltr.v + j * a.ltr_nc};
+}
+
 // K5 sub-slices (h264_encoder.h intra_split): does slice t code as sub-slices, and how
 // many NALs does it produce this frame (0: not coded).
 __device__ __forceinline__ bool split_i(const FrameArgs& a, const SliceTask& t) {
@@ -599,7 +607,7 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
     const int dev = mb_activity(sw);   // scene-cut intra estimate
     int refi = 0;
     if (t.num_refs > 1 && a.mb_dirty[idx]) {   // second reference at the zero vector (CPU: same rule)
-        const int s1 = me_sad(a, a.ref1.y, sw, mbx, mby, 0, 0, ylo, yhi);
+        const int s1 = me_sad(a, ref1_planes(a, mby / a.rows_per_slice).y, sw, mbx, mby, 0, 0, ylo, yhi);
         if (s1 + 3 * lam < bcost) {
             bx = by = 0;
             bsad = s1;
@@ -839,8 +847,19 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
             for (int s = tid; s < ns; s += 256) idr &= a.tasks[s].final_action == ACT_I && a.tasks[s].idr_on_intra;
             idr = __syncthreads_and(idr);
             if (tid == 0) commit_picture(pic, idr, a.plan_cfg.num_refs);
+            if (a.ltr_slots && tid == 0)   // long-term cache: current slot and the marking model (ltr.h)
+                ltr::ltr_commit(a.ltr_slots, a.ltr_state[ns], true, idr, a.tasks[0].frame_num, a.mb_w * a.mb_h, 0, ns,
+                                a.ltr_task);
         } else {
-            for (int s = tid; s < ns; s += 256) commit_stripe(st[s], a.tasks[s].final_action, a.plan_cfg.num_refs);
+            if (a.ltr_slots)
+                for (int s = tid; s < ns; s += 256) {
+                    const SliceTask& t = a.tasks[s];
+                    ltr::ltr_commit(a.ltr_slots, a.ltr_state[s], t.final_action != ACT_NONE,
+                                    t.final_action == ACT_I && t.idr_on_intra, t.frame_num, t.num_rows * a.mb_w, s, s + 1,
+                                    a.ltr_task);
+                }
+            for (int s = tid; s < ns; s += 256)
+                commit_stripe(st[s], a.tasks[s].final_action, a.plan_cfg.num_refs, a.tasks[s].idr_on_intra != 0);
         }
     }
     // host overrides: the device copy of the host-mapped snapshot that the damage kernel
@@ -879,6 +898,91 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Long-term reference cache (codec/ltr.h), between k_plan and the motion search.
+// k_ltr_match: one workgroup per (MB row of a slice, reference column, slice); column 0
+// is the current reference, 1 + j slot j. Every workgroup counts the dirty MBs of its
+// slice's stream (the stripe, or the whole picture in full-frame mode) and leaves after
+// that unless the frame is gated (large change, planned P, a valid slot): no cache memory
+// is touched on other frames. Gated, it sums the zero-vector luma SAD of its MB row
+// (v_sad_u8 on 16-byte loads; exact integers, so the CPU decides the same).
+__global__ __launch_bounds__(256) void k_ltr_match(FrameArgs a) {
+    __shared__ int red[4];
+    const int band = blockIdx.x, c = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
+    const int ns = a.num_slices;
+    const SliceTask t = a.tasks[s];
+    const int s0 = a.fullframe ? 0 : s, s1 = a.fullframe ? ns : s + 1;
+    const int mb0 = (a.fullframe ? 0 : t.first_row) * a.mb_w, n = (a.fullframe ? a.mb_h : t.num_rows) * a.mb_w;
+    int nd = 0, key = 0, anyp = 0;
+    for (int i = tid; i < n; i += 256) nd += a.mb_dirty[mb0 + i] != 0;
+    for (int i = s0 + tid; i < s1; i += 256) {
+        key |= a.tasks[i].action == ACT_I;
+        anyp |= a.tasks[i].action == ACT_P;
+    }
+    nd = wave_sum(nd);
+    if (lane_id() == 0) red[tid >> 6] = nd;
+    key = __syncthreads_or(key);
+    anyp = __syncthreads_or(anyp);
+    nd = red[0] + red[1] + red[2] + red[3];
+    const int valid = a.ltr_state[a.fullframe ? ns : s].valid;
+    const bool gate = anyp && !key && ltr::ltr_large(nd, n) && valid != 0;
+    if (band == 0 && c == 0 && tid == 0) {
+        a.ltr_cnt[2 * s] = nd;
+        a.ltr_cnt[2 * s + 1] = gate;
+    }
+    if (!gate || t.action != ACT_P || band >= t.num_rows || (c > 0 && !((valid >> (c - 1)) & 1))) return;
+    const uint8_t* ref = c ? a.ltr.y + (size_t)(c - 1) * a.ltr_ny : a.ref.y;
+    const size_t o = (size_t)(t.first_row + band) * 16 * a.stride_y;
+    const uint4* q = reinterpret_cast<const uint4*>(a.src.y + o);
+    const uint4* r = reinterpret_cast<const uint4*>(ref + o);
+    uint32_t sum = 0;
+    for (int i = tid; i < a.stride_y; i += 256) {   // 16 rows of stride_y bytes = stride_y 16-byte words
+        const uint4 x = q[i], y = r[i];
+        sum = __builtin_amdgcn_sad_u8(x.x, y.x, sum);
+        sum = __builtin_amdgcn_sad_u8(x.y, y.y, sum);
+        sum = __builtin_amdgcn_sad_u8(x.z, y.z, sum);
+        sum = __builtin_amdgcn_sad_u8(x.w, y.w, sum);
+    }
+    sum = (uint32_t)wave_sum((int)sum);
+    __syncthreads();   // red was read above
+    if (lane_id() == 0) red[tid >> 6] = (int)sum;
+    __syncthreads();
+    if (tid == 0)
+        a.ltr_part[((size_t)s * ltr::kLtrSadCols + c) * a.rows_per_slice + band] =
+            (uint32_t)red[0] + (uint32_t)red[1] + (uint32_t)red[2] + (uint32_t)red[3];
+}
+
+// k_ltr_decide (one workgroup): the MB-row sums of the gated slices, then ltr_decide with one
+// lane per stream into LtrTask / LtrState; a slice that chose a slot codes with two references.
+__global__ __launch_bounds__(256) void k_ltr_decide(FrameArgs a) {
+    const int ns = a.num_slices, tid = threadIdx.x;
+    for (int i = tid; i < ns * ltr::kLtrSadCols; i += 256) {
+        const int s = i / ltr::kLtrSadCols, c = i - s * ltr::kLtrSadCols;
+        const int valid = a.ltr_state[a.fullframe ? ns : s].valid;
+        uint32_t sum = 0;
+        if (a.ltr_cnt[2 * s + 1] && a.tasks[s].action == ACT_P && c <= a.ltr_slots && (c == 0 || ((valid >> (c - 1)) & 1)))
+            for (int b = 0; b < a.tasks[s].num_rows; b++) sum += a.ltr_part[(size_t)i * a.rows_per_slice + b];
+        a.ltr_sad[i] = sum;
+    }
+    __syncthreads();
+    const int streams = a.fullframe ? 1 : ns;
+    for (int k = tid; k < streams; k += 256) {
+        const int s0 = a.fullframe ? 0 : k, s1 = a.fullframe ? ns : k + 1;
+        bool key = false, anyp = false;
+        int rows = 0;
+        for (int s = s0; s < s1; s++) {
+            key |= a.tasks[s].action == ACT_I;
+            anyp |= a.tasks[s].action == ACT_P;
+            rows += a.tasks[s].num_rows;
+        }
+        ltr::ltr_decide(a.ltr_slots, a.ltr_state[a.fullframe ? ns : k], a.ltr_cnt[2 * s0], rows * a.mb_w, anyp && !key,
+                        a.tasks[s0].frame_num, kFrameNumMask, s0, s1,
+                        [&](int s) { return a.tasks[s].action == ACT_P; }, a.ltr_sad, a.ltr_task);
+        for (int s = s0; s < s1; s++)
+            if (a.ltr_task[s].slot >= 0) a.tasks[s].num_refs = 2;   // [previous picture, the slot]
+    }
+}
+
 // One workgroup per slice: scene-cut decision from the per-MB ME results.
 __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
     __shared__ long long red[2][4];
@@ -886,14 +990,21 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
     SliceTask& t = a.tasks[s];
     const bool planned_p = t.action == ACT_P;
     const bool p = planned_p && t.allow_scenecut;
+    __shared__ int red1[4];
     long long sad = 0, dev = 0;
+    int ref1 = 0;   // MBs coded from the slice's cached picture (long-term cache: the stream's cur_slot)
     if (planned_p || t.action == ACT_I) {   // planned key frames: activity only (sad 0)
         const int first = t.first_row * a.mb_w, nmb = t.num_rows * a.mb_w;
         for (int i = threadIdx.x; i < nmb; i += 256) {
             const MeResult r = a.me[first + i];
             sad += r.sad;
             dev += r.intra_est;
+            ref1 += r.ref == 1;
         }
+    }
+    if (a.ltr_slots) {
+        for (int o = 32; o > 0; o >>= 1) ref1 += __shfl_down(ref1, o);
+        if (lane_id() == 0) red1[threadIdx.x >> 6] = ref1;
     }
     for (int o = 32; o > 0; o >>= 1) {
         sad += __shfl_down(sad, o);
@@ -908,6 +1019,8 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
         const long long ts = red[0][0] + red[0][1] + red[0][2] + red[0][3];
         const long long td = red[1][0] + red[1][1] + red[1][2] + red[1][3];
         t.final_action = (p && ts > td) ? ACT_I : t.action;
+        if (a.ltr_slots)
+            a.ltr_task[s].ref1_mbs = (planned_p && t.final_action == ACT_P) ? red1[0] + red1[1] + red1[2] + red1[3] : 0;
         a.rc_slice[2 * s] = ts;       // K10 complexity (k_rc_qp)
         a.rc_slice[2 * s + 1] = td;
         a.tasks_host[s] = t;  // final decision back to the host (host-mapped)
@@ -1765,7 +1878,7 @@ __global__ __launch_bounds__(256) void k_subpel(FrameArgs a) {
         return;
     }
     const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
-    qpel_fill_fast(Q, r.ref ? a.ref1.y : a.ref.y, a.stride_y, a.stride_y, ylo, yhi, mbx * 16 + r.mvx - 3,
+    qpel_fill_fast(Q, r.ref ? ref1_planes(a, sl).y : a.ref.y, a.stride_y, a.stride_y, ylo, yhi, mbx * 16 + r.mvx - 3,
               mby * 16 + r.mvy - 3);
     const int yy = l >> 2, xx = 4 * (l & 3);
     const uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + yy) * a.stride_y +
@@ -1845,7 +1958,7 @@ __global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
     MvNb C = nbr(mbx + 1, mby - 1, top && mbx + 1 < a.mb_w);
     if (!C.avail) C = nbr(mbx - 1, mby - 1, top && mbx > 0);
     const int refi = a.me[idx].ref;
-    const Planes& rp = refi ? a.ref1 : a.ref;
+    const Planes rp = refi ? ref1_planes(a, s) : a.ref;
     int pmx, pmy, smx, smy;
     mv_pred16x16(A, B, C, refi, &pmx, &pmy);
     mv_pskip(A, B, C, &smx, &smy);
@@ -2748,6 +2861,15 @@ __global__ __launch_bounds__(256) void k_slice_scan(FrameArgs a) {
         h.slice_qp = task.qp;
         h.deblock = slice_deblock(a.deblock, task);
         h.num_refs = intra ? 1 : task.num_refs;
+        if (a.ltr_slots) {   // long-term cache: list modification / marking, as the CPU writer
+            const ltr::LtrTask L = a.ltr_task[s];
+            if (fin == ACT_P) h.lt_ref = L.slot;
+            if (!idr && L.store_slot >= 0) {
+                h.lt_store = L.store_slot;
+                h.lt_max_idx = a.ltr_slots;
+                h.st_drop = L.mmco1;
+            }
+        }
         write_slice_header(w, h);
         if (fin == ACT_SKIPALL) put_ue(w, (uint32_t)nmb);
         sh_misc[0] = (int)w.pos;
@@ -3059,6 +3181,11 @@ __global__ __launch_bounds__(256) void k_commit(FrameArgs a) {
     // sliding-window DPB: the current reference becomes reference 1 (a skip-all picture
     // is a reference too); the same thread then overwrites ref with rec below
     if (a.num_refs > 1) copy(a.ref, a.ref1);
+    if (a.ltr_slots) {   // long-term store: the previous picture's rows go to the slot before rec replaces them
+        const int j = a.ltr_task[s].store_slot;
+        if (j >= 0) copy(a.ref, Planes{a.ltr.y + (size_t)j * a.ltr_ny, a.ltr.u + (size_t)j * a.ltr_nc,
+                                       a.ltr.v + (size_t)j * a.ltr_nc});
+    }
     if (fin == ACT_SKIPALL || slice_deblock(a.deblock, a.tasks[s])) return;  // reference unchanged / written by k_deblock
     copy(a.rec, a.ref);
 }
@@ -3380,6 +3507,10 @@ void launch_convert_damage(const FrameArgs& a, hipStream_t s) {
 void launch_frontend(const FrameArgs& a, hipStream_t s) {
     int nmb = a.mb_w * a.mb_h;
     hipLaunchKernelGGL(k_plan, dim3(1), dim3(256), 0, s, a);
+    if (a.ltr_slots) {   // long-term cache: these two nodes exist only with EncoderConfig::ltr_slots > 0
+        hipLaunchKernelGGL(k_ltr_match, dim3(a.rows_per_slice, 1 + a.ltr_slots, a.num_slices), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_ltr_decide, dim3(1), dim3(256), 0, s, a);
+    }
     if (a.me_full) hipLaunchKernelGGL(k_me, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_motion_search, dim3(nmb), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_decide, dim3(a.num_slices), dim3(256), 0, s, a);

@@ -114,13 +114,16 @@ class CaptureSession {
                 e.rc_mode = s.h264_rc_mode >= 0 && s.h264_rc_mode <= 2 ? s.h264_rc_mode : h264::RC_CQP;
                 e.bitrate_kbps = s.h264_bitrate_kbps > 0 ? s.h264_bitrate_kbps : 0;
                 if (e.rc_mode == h264::RC_CBR && e.bitrate_kbps <= 0) e.rc_mode = h264::RC_CRF;
+                e.ltr_slots = sk_clip(s.h264_ltr_slots, 0, ltr::kLtrMaxSlots);
                 if (s.output_mode == 2 || s.output_mode == 3) {   // HEVC / AV1: full-frame pictures
                     e.codec = s.output_mode == 2 ? 1 : 2;
                     e.fullframe = 1;
                     e.aq_strength = 0;
                     e.intra4x4 = 0;
+                    e.ltr_slots = 0;
                     e.deblock = 0;   // their own in-loop filters, not the H.264 front end's
                 }
+                if (const char* err = h264::ltr_config_error(e)) throw std::runtime_error(err);
                 ecfg_ = e;
                 enc_.reset(backend ? create_hip_backend(e, s.device) : create_cpu_backend(e));
             }

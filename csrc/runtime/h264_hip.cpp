@@ -337,7 +337,29 @@ class HipBackend : public EncoderBackend {
         return (int)packets_.size();
     }
 
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(g_); }
+    int64_t state_bytes() override { return (int64_t)h264::state_bytes(g_, args_.ltr_slots); }
+
+    // Long-term cache state as the CPU back end holds it after a frame: the device copy, with the
+    // commit k_plan would run at the next frame applied (ctl1 == 1).
+    std::vector<ltr::LtrState> committed_ltr_state(int ctl1, const std::vector<SliceTask>& tasks) {
+        const int ns = g_.num_slices, slots = args_.ltr_slots;
+        std::vector<ltr::LtrState> ls(ns + 1);
+        std::vector<ltr::LtrTask> lt(ns);
+        copy_now(ls.data(), args_.ltr_state, sizeof(ltr::LtrState) * (ns + 1));
+        copy_now(lt.data(), args_.ltr_task, sizeof(ltr::LtrTask) * ns);
+        if (ctl1 != 1) return ls;
+        if (cfg_.fullframe) {
+            bool idr = ns > 0;
+            for (int s = 0; s < ns; s++) idr &= tasks[s].final_action == ACT_I && tasks[s].idr_on_intra;
+            ltr::ltr_commit(slots, ls[ns], true, idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
+        } else {
+            for (int s = 0; s < ns; s++)
+                ltr::ltr_commit(slots, ls[s], tasks[s].final_action != ACT_NONE,
+                                tasks[s].final_action == ACT_I && tasks[s].idr_on_intra, tasks[s].frame_num,
+                                tasks[s].num_rows * g_.mb_w, s, s + 1, lt.data());
+        }
+        return ls;
+    }
 
     // Copies `n` bytes between this encoder's device buffer and a caller buffer
     // that is device (on_device) or host memory.
@@ -363,7 +385,8 @@ class HipBackend : public EncoderBackend {
                 for (int s = 0; s < ns; s++) idr &= tasks[s].final_action == ACT_I && tasks[s].idr_on_intra;
                 commit_picture(st[ns], idr, cfg_.num_refs > 1 ? 2 : 1);
             } else {
-                for (int s = 0; s < ns; s++) commit_stripe(st[s], tasks[s].final_action, cfg_.num_refs > 1 ? 2 : 1);
+                for (int s = 0; s < ns; s++)
+                    commit_stripe(st[s], tasks[s].final_action, cfg_.num_refs > 1 ? 2 : 1, tasks[s].idr_on_intra != 0);
             }
         }
         const int qp = h_key_seq_[1] > 0 ? h_key_seq_[1] : cfg_.qp;
@@ -386,6 +409,20 @@ class HipBackend : public EncoderBackend {
             xfer(o, pl->v, nc, true, on_device); o += nc;
         }
         xfer(o, args_.mvfield, sizeof(int16_t) * 2 * (size_t)g_.num_mbs(), true, on_device);
+        o += sizeof(int16_t) * 2 * (size_t)g_.num_mbs();
+        std::vector<ltr::LtrState> ls;   // alive until the copies below are done
+        if (args_.ltr_slots) {   // version 4: LtrState[] and the slot plane sets follow
+            ls = committed_ltr_state(ctl[1], tasks);
+            const size_t nb = sizeof(ltr::LtrState) * ls.size();
+            if (on_device) HIPCHECK(hipMemcpyAsync(o, ls.data(), nb, hipMemcpyHostToDevice, stream_));
+            else memcpy(o, ls.data(), nb);
+            o += nb;
+            for (int j = 0; j < args_.ltr_slots; j++) {
+                xfer(o, args_.ltr.y + j * ny, ny, true, on_device); o += ny;
+                xfer(o, args_.ltr.u + j * nc, nc, true, on_device); o += nc;
+                xfer(o, args_.ltr.v + j * nc, nc, true, on_device); o += nc;
+            }
+        }
         HIPCHECK(hipStreamSynchronize(stream_));
         return 0;
     }
@@ -421,6 +458,16 @@ class HipBackend : public EncoderBackend {
             xfer(pl->v, i, nc, false, on_device); i += nc;
         }
         xfer(args_.mvfield, i, sizeof(int16_t) * 2 * (size_t)g_.num_mbs(), false, on_device);
+        i += sizeof(int16_t) * 2 * (size_t)g_.num_mbs();
+        if (args_.ltr_slots) {
+            xfer(args_.ltr_state, i, sizeof(ltr::LtrState) * (ns + 1), false, on_device);
+            i += sizeof(ltr::LtrState) * (ns + 1);
+            for (int j = 0; j < args_.ltr_slots; j++) {
+                xfer(args_.ltr.y + j * ny, i, ny, false, on_device); i += ny;
+                xfer(args_.ltr.u + j * nc, i, nc, false, on_device); i += nc;
+                xfer(args_.ltr.v + j * nc, i, nc, false, on_device); i += nc;
+            }
+        }
         // controller: committed state (2), and the host keyframe counter as already seen
         int ctl[2] = {__atomic_load_n(&h_key_seq_[0], __ATOMIC_SEQ_CST), h.started ? 2 : 0};
         HIPCHECK(hipMemcpyAsync(args_.plan_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, stream_));
@@ -479,6 +526,20 @@ class HipBackend : public EncoderBackend {
         else if (s == "ref_u") { p = args_.ref.u; n = (int64_t)nc; }
         else if (s == "ref_v") { p = args_.ref.v; n = (int64_t)nc; }
         else if (s == "ref1_y") { p = args_.ref1.y; n = (int64_t)ny; }
+        else if (s == "ltr_task" && args_.ltr_slots) { p = args_.ltr_task; n = (int64_t)g_.num_slices * sizeof(ltr::LtrTask); }
+        else if (s == "ltr_state" && args_.ltr_slots) {
+            const int ns = g_.num_slices;
+            int ctl[4];
+            std::vector<SliceTask> tasks(ns);
+            copy_now(ctl, args_.plan_ctl, sizeof(ctl));
+            copy_now(tasks.data(), args_.tasks, sizeof(SliceTask) * ns);
+            const std::vector<ltr::LtrState> ls = committed_ltr_state(ctl[1], tasks);
+            n = (int64_t)(ls.size() * sizeof(ltr::LtrState));
+            if (dst && cap >= n) memcpy(dst, ls.data(), (size_t)n);
+            return n;
+        }
+        else if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
+                 s[3] < '0' + args_.ltr_slots) { p = args_.ltr.y + (size_t)(s[3] - '0') * ny; n = (int64_t)ny; }
         else if (s == "fs_mv") { p = args_.fs_mv; n = (int64_t)g_.num_mbs() * 4; }
         else if (s == "mbs") { p = args_.mbs; n = (int64_t)g_.num_mbs() * sizeof(MbInfo); }
         else if (s == "blk" && cfg_.codec == 2) { p = aargs_.blk; n = (int64_t)av1_geo_.c8 * av1_geo_.r8 * sizeof(av1::BlkInfo); }
@@ -578,6 +639,28 @@ class HipBackend : public EncoderBackend {
         a.ref = make_planes();
         a.ref1 = make_planes();
         a.rec = make_planes();
+        a.ltr_slots = ltr_slots_of(cfg_);
+        if (a.ltr_slots) {   // long-term cache (codec/ltr.h): slot plane sets, stream states, per-frame decisions
+            const size_t ny = (size_t)g_.stride_y * g_.plane_h_y, nc = (size_t)g_.stride_c * g_.plane_h_c;
+            a.ltr_ny = ny;
+            a.ltr_nc = nc;
+            a.ltr.y = dmalloc<uint8_t>(ny * a.ltr_slots);
+            a.ltr.u = dmalloc<uint8_t>(nc * a.ltr_slots);
+            a.ltr.v = dmalloc<uint8_t>(nc * a.ltr_slots);
+            ltr::LtrState z;
+            ltr::ltr_state_reset(z);
+            std::vector<ltr::LtrState> init(ns + 1, z);
+            a.ltr_state = dmalloc<ltr::LtrState>(ns + 1);
+            copy_now(a.ltr_state, init.data(), sizeof(ltr::LtrState) * (ns + 1));
+            ltr::LtrTask zt;
+            ltr::ltr_task_reset(zt);
+            std::vector<ltr::LtrTask> tinit(ns, zt);
+            a.ltr_task = dmalloc<ltr::LtrTask>(ns);
+            copy_now(a.ltr_task, tinit.data(), sizeof(ltr::LtrTask) * ns);
+            a.ltr_part = dmalloc<uint32_t>((size_t)ns * ltr::kLtrSadCols * g_.rows_per_slice);
+            a.ltr_sad = dmalloc<uint32_t>((size_t)ns * ltr::kLtrSadCols);
+            a.ltr_cnt = dmalloc<int>(2 * (size_t)ns);
+        }
         a.mb_dirty = dmalloc<uint8_t>(nmb);
         void* dd = nullptr;
         a.stripe_dirty = dmalloc<int>(ns);
@@ -649,10 +732,12 @@ class HipBackend : public EncoderBackend {
         std::vector<std::vector<uint8_t>> ps;
         if (cfg_.fullframe) {
             ps.resize(1);
-            build_parameter_sets(g_.W, g_.H, cfg_.full_range, cfg_.fps, ps[0], cfg_.num_refs);
+            build_parameter_sets(g_.W, g_.H, cfg_.full_range, cfg_.fps, ps[0], cfg_.num_refs, ltr_slots_of(cfg_));
         } else {
             ps.resize(ns);
-            for (int s = 0; s < ns; s++) build_parameter_sets(g_.W, g_.slice_pix_h(s), cfg_.full_range, cfg_.fps, ps[s], cfg_.num_refs);
+            for (int s = 0; s < ns; s++)
+                build_parameter_sets(g_.W, g_.slice_pix_h(s), cfg_.full_range, cfg_.fps, ps[s], cfg_.num_refs,
+                                     ltr_slots_of(cfg_));
         }
         param_sets_ = ps;
         a.param_set_stride = 256;
@@ -995,7 +1080,7 @@ class HipBackend : public EncoderBackend {
             pk.y = g_.slice_pix_y(s);
             pk.w = g_.W;
             pk.h = g_.slice_pix_h(s);
-            pk.key = h_tasks[s].final_action == ACT_I;
+            pk.key = h_tasks[s].final_action == ACT_I && h_tasks[s].idr_on_intra;   // non-IDR I: long-term cache on
             const uint8_t* p = host_out + offs[s];
             pk.data.assign(p, p + h_out_size[s]);
             packets_.push_back(std::move(pk));

@@ -59,6 +59,16 @@ int cpu_export_state(h264::CpuH264Encoder& e, void* dst, int on_device) {
             o += planes[p].size();
         }
     memcpy(o, e.mvfield.data(), e.mvfield.size() * sizeof(int16_t));
+    o += e.mvfield.size() * sizeof(int16_t);
+    if (e.ltr_slots_) {   // version 4: the long-term cache follows the version-3 layout
+        memcpy(o, e.ltr_state.data(), e.ltr_state.size() * sizeof(ltr::LtrState));
+        o += e.ltr_state.size() * sizeof(ltr::LtrState);
+        for (int j = 0; j < e.ltr_slots_; j++)
+            for (int p = 0; p < 3; p++) {
+                memcpy(o, e.ltr_planes[j][p].data(), e.ltr_planes[j][p].size());
+                o += e.ltr_planes[j][p].size();
+            }
+    }
     return 0;
 }
 
@@ -82,6 +92,16 @@ int cpu_import_state(h264::CpuH264Encoder& e, const void* src, int on_device) {
             i += planes[p].size();
         }
     memcpy(e.mvfield.data(), i, e.mvfield.size() * sizeof(int16_t));
+    i += e.mvfield.size() * sizeof(int16_t);
+    if (e.ltr_slots_) {
+        memcpy(e.ltr_state.data(), i, e.ltr_state.size() * sizeof(ltr::LtrState));
+        i += e.ltr_state.size() * sizeof(ltr::LtrState);
+        for (int j = 0; j < e.ltr_slots_; j++)
+            for (int p = 0; p < 3; p++) {
+                memcpy(e.ltr_planes[j][p].data(), i, e.ltr_planes[j][p].size());
+                i += e.ltr_planes[j][p].size();
+            }
+    }
     e.first_frame = !h.started;
     e.set_qp(h.qp, h.paint_qp);
     return 0;
@@ -130,6 +150,10 @@ class CpuBackend : public EncoderBackend {
         else if (s == "ref_u") plane(enc_.ref[1]);
         else if (s == "ref_v") plane(enc_.ref[2]);
         else if (s == "ref1_y") plane(enc_.ref1[0]);
+        else if (s == "ltr_state") { p = enc_.ltr_state.data(); n = (int64_t)(enc_.ltr_state.size() * sizeof(ltr::LtrState)); }
+        else if (s == "ltr_task") { p = enc_.ltr_task.data(); n = (int64_t)(enc_.ltr_task.size() * sizeof(ltr::LtrTask)); }
+        else if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
+                 s[3] < '0' + enc_.ltr_slots_) plane(enc_.ltr_planes[s[3] - '0'][0]);
         else if (s == "mbs") { p = enc_.mbs.data(); n = (int64_t)(enc_.mbs.size() * sizeof(h264::MbInfo)); }
         else if (s == "coefs") { p = enc_.coefs.data(); n = (int64_t)(enc_.coefs.size() * 2); }
         else if (s == "me") { p = enc_.me.data(); n = (int64_t)(enc_.me.size() * sizeof(h264::MeResult)); }
@@ -142,7 +166,7 @@ class CpuBackend : public EncoderBackend {
         return n;
     }
 
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(enc_.g); }
+    int64_t state_bytes() override { return (int64_t)h264::state_bytes(enc_.g, enc_.ltr_slots_); }
     int export_state(void* dst, int on_device) override { return cpu_export_state(enc_, dst, on_device); }
     int import_state(const void* src, int on_device) override { return cpu_import_state(enc_, src, on_device); }
 
@@ -339,11 +363,13 @@ h264::EncoderConfig to_config(const sk_h264_config* c) {
     e.aq_strength = c->aq_strength > 0 ? (c->aq_strength > 64 ? 64 : c->aq_strength) : 0;
     e.subpel = c->subpel >= 0 ? 1 : 0;
     e.intra4x4 = c->intra4x4 > 0 ? 1 : 0;
+    e.ltr_slots = c->ltr_slots > 0 ? c->ltr_slots : 0;
     if (e.codec >= 1) {   // HEVC / AV1: full-frame pictures, slices of whole CTB rows, one reference
         e.aq_strength = 0;   // no cu_qp_delta in this HEVC profile setup
         e.fullframe = 1;
         e.num_refs = 1;
         e.deblock = 0;
+        e.ltr_slots = 0;
     }
     return e;
 }
@@ -403,6 +429,10 @@ void* sk_h264_create(const sk_h264_config* c) {
         return nullptr;
     }
     h264::EncoderConfig e = to_config(c);
+    if (const char* err = h264::ltr_config_error(e)) {   // long-term reference cache (codec/ltr.h)
+        set_last_error(err);
+        return nullptr;
+    }
     try {
         if (c->backend == 1) return create_hip_backend(e, c->device);
         return create_cpu_backend(e);

@@ -5,7 +5,10 @@ bitstream conformance is checked against this independent implementation of
 the decoding process of ITU-T H.264 clauses 7 (syntax), 8 (decoding) and 9.2
 (CAVLC). It supports exactly what a Baseline stream from our encoder may contain
 plus a little more (I_PCM, quarter-pel luma MC), and raises NotImplementedError
-for the rest (CABAC, interlace, FMO/ASO, B slices, in-loop deblocking).
+for the rest (CABAC, interlace, FMO/ASO, B slices, MMCO 5). Reference lists and
+marking for frames are complete (RefMarking: short- and long-term pictures, list
+modification, MMCO 1-4 and 6, sliding window); what a stream may not do there
+(name a missing picture, overfill the DPB) raises BitstreamError.
 
 Pure Python + numpy; intended for test-sized pictures.
 """
@@ -385,6 +388,133 @@ class MbState:
     db: tuple = (1, 0, 0)  # (disable_deblocking_filter_idc, FilterOffsetA, FilterOffsetB) of its slice
 
 
+class RefFrame:
+    """A reference frame in the DPB. Frames only, so PicNum = FrameNumWrap and
+    LongTermPicNum = LongTermFrameIdx (8.2.4.1)."""
+
+    __slots__ = ("frame_num", "long_term_idx", "planes")
+
+    def __init__(self, frame_num: int, planes=None, long_term_idx=None):
+        self.frame_num = frame_num
+        self.long_term_idx = long_term_idx   # None: short-term
+        self.planes = planes
+
+    def __repr__(self):
+        return f"LT{self.long_term_idx}" if self.long_term_idx is not None else f"ST{self.frame_num}"
+
+
+class RefMarking:
+    """Reference picture lists (8.2.4) and decoded reference picture marking (8.2.5) for a
+    stream of frames. Short-term and long-term frames are kept apart; every rule that names
+    a picture which is not in the DPB, and a DPB over its bound, raises BitstreamError."""
+
+    def __init__(self):
+        self.short: list[RefFrame] = []   # decoding order
+        self.long: list[RefFrame] = []
+        self.max_lt_idx = -1              # MaxLongTermFrameIdx; -1 = "no long-term frame indices"
+
+    @staticmethod
+    def pic_num(f: RefFrame, frame_num: int, max_frame_num: int) -> int:
+        """FrameNumWrap = PicNum of short-term frame f seen from a picture with `frame_num` (8-27, 8-28)."""
+        return f.frame_num - max_frame_num if f.frame_num > frame_num else f.frame_num
+
+    def initial_list(self, frame_num: int, max_frame_num: int) -> list:
+        """8.2.4.2.1: short-term frames by descending PicNum, then long-term by ascending LongTermPicNum."""
+        st = sorted(self.short, key=lambda f: -self.pic_num(f, frame_num, max_frame_num))
+        lt = sorted(self.long, key=lambda f: f.long_term_idx)
+        return st + lt
+
+    def _short_by_pic_num(self, pic_num: int, frame_num: int, max_frame_num: int, what: str) -> RefFrame:
+        for f in self.short:
+            if self.pic_num(f, frame_num, max_frame_num) == pic_num:
+                return f
+        raise BitstreamError(f"{what}: no short-term reference picture with PicNum {pic_num}")
+
+    def _long_by_idx(self, idx: int, what: str) -> RefFrame:
+        for f in self.long:
+            if f.long_term_idx == idx:
+                return f
+        raise BitstreamError(f"{what}: no long-term reference picture with LongTermPicNum {idx}")
+
+    def build_list(self, frame_num: int, max_frame_num: int, num_ref: int, mods=()) -> list:
+        """RefPicList0 of a P slice: the initial list cut or padded (None = "no reference
+        picture") to num_ref entries, then ref_pic_list_modification (8.2.4.3). `mods` holds
+        (modification_of_pic_nums_idc, value) pairs: idc 0 / 1 with abs_diff_pic_num_minus1,
+        idc 2 with long_term_pic_num."""
+        lst = self.initial_list(frame_num, max_frame_num)[:num_ref]
+        lst += [None] * (num_ref - len(lst))
+        if len(mods) > num_ref:
+            raise BitstreamError("more list modifications than active references")
+        pred = frame_num   # picNumL0Pred starts at CurrPicNum
+        for idx, (idc, val) in enumerate(mods):
+            if idc in (0, 1):
+                d = val + 1
+                if idc == 0:   # (8-34)
+                    pred = pred - d + (max_frame_num if pred - d < 0 else 0)
+                else:          # (8-35)
+                    pred = pred + d - (max_frame_num if pred + d >= max_frame_num else 0)
+                pn = pred - max_frame_num if pred > frame_num else pred   # (8-36)
+                f = self._short_by_pic_num(pn, frame_num, max_frame_num, "ref_pic_list_modification")
+            elif idc == 2:
+                f = self._long_by_idx(val, "ref_pic_list_modification")
+            else:
+                raise BitstreamError(f"modification_of_pic_nums_idc {idc}")
+            # (8-37) / (8-38): f moves to position idx, the rest shifts back, its later copy goes
+            rest = [g for g in lst[idx:] if g is not f]
+            lst = (lst[:idx] + [f] + rest)[:num_ref]
+        return lst
+
+    def mark(self, cur: RefFrame, idr: bool, max_frame_num: int, max_num_ref_frames: int, mmco=None,
+             long_term_reference_flag: bool = False) -> None:
+        """Marking after `cur` (a reference picture) was decoded. mmco: None for the sliding
+        window (8.2.5.3), else the picture's memory_management_control_operations as tuples
+        (op, arguments...) without the terminating 0 (8.2.5.4)."""
+        fn = cur.frame_num
+        bound = max(max_num_ref_frames, 1)
+        if idr:
+            self.short, self.long = [], []
+            if long_term_reference_flag:
+                cur.long_term_idx = 0
+                self.max_lt_idx = 0
+            else:
+                self.max_lt_idx = -1
+        elif mmco is None:
+            if len(self.short) + len(self.long) >= bound:
+                if not self.short:
+                    raise BitstreamError("sliding window: the DPB is full of long-term pictures")
+                self.short.remove(min(self.short, key=lambda f: self.pic_num(f, fn, max_frame_num)))
+        else:
+            for op in mmco:
+                if op[0] == 1:     # short-term picture -> unused (8.2.5.4.1)
+                    self.short.remove(self._short_by_pic_num(fn - (op[1] + 1), fn, max_frame_num, "MMCO 1"))
+                elif op[0] == 2:   # long-term picture -> unused (8.2.5.4.2)
+                    self.long.remove(self._long_by_idx(op[1], "MMCO 2"))
+                elif op[0] == 3:   # short-term picture -> long-term frame index (8.2.5.4.3)
+                    f = self._short_by_pic_num(fn - (op[1] + 1), fn, max_frame_num, "MMCO 3")
+                    if op[2] > self.max_lt_idx:
+                        raise BitstreamError(f"MMCO 3: long_term_frame_idx {op[2]} > MaxLongTermFrameIdx")
+                    self.long = [g for g in self.long if g.long_term_idx != op[2]]
+                    self.short.remove(f)
+                    f.long_term_idx = op[2]
+                    self.long.append(f)
+                elif op[0] == 4:   # MaxLongTermFrameIdx (8.2.5.4.4)
+                    self.max_lt_idx = op[1] - 1
+                    self.long = [g for g in self.long if g.long_term_idx <= self.max_lt_idx]
+                elif op[0] == 6:   # the current picture -> long-term frame index (8.2.5.4.6)
+                    if op[1] > self.max_lt_idx:
+                        raise BitstreamError(f"MMCO 6: long_term_frame_idx {op[1]} > MaxLongTermFrameIdx")
+                    self.long = [g for g in self.long if g.long_term_idx != op[1]]
+                    cur.long_term_idx = op[1]
+                elif op[0] == 5:
+                    raise NotImplementedError("memory_management_control_operation 5")
+                else:
+                    raise BitstreamError(f"memory_management_control_operation {op[0]}")
+        (self.long if cur.long_term_idx is not None else self.short).append(cur)
+        if len(self.short) + len(self.long) > bound:
+            raise BitstreamError(f"DPB holds {len(self.short) + len(self.long)} reference frames, "
+                                 f"max_num_ref_frames allows {bound}")
+
+
 class H264Decoder:
     """Decodes an Annex-B stream; `decode(data)` returns a list of decoded frames
     as (Y, U, V) uint8 arrays cropped to the SPS display size."""
@@ -392,7 +522,9 @@ class H264Decoder:
     def __init__(self):
         self.sps: dict[int, SPS] = {}
         self.pps: dict[int, PPS] = {}
-        self.dpb: list = []      # short-term reference pictures (Y, U, V), most recent first (8.2.4.2.1)
+        self.marking = RefMarking()   # the DPB's reference frames (8.2.5)
+        self.ref_list: list = []      # RefPicList0 of the current slice: (Y, U, V) or None per index
+        self.cur_marking = None       # dec_ref_pic_marking() of the current picture's first slice
         self.cur_ref_idc = 0
         self.cur_idr = False
         self.cur = None
@@ -446,10 +578,10 @@ class H264Decoder:
         x0, y0 = 2 * cl, 2 * ct
         self.frames.append((y[y0:y0 + H, x0:x0 + W].copy(), u[y0 // 2:(y0 + H) // 2, x0 // 2:(x0 + W) // 2].copy(),
                             v[y0 // 2:(y0 + H) // 2, x0 // 2:(x0 + W) // 2].copy()))
-        if self.cur_ref_idc:   # sliding-window marking (8.2.5.3); IDR empties the DPB first
-            pic = (y.copy(), u.copy(), v.copy())
-            self.dpb = [pic] if self.cur_idr else [pic] + self.dpb
-            del self.dpb[max(1, sps.max_num_ref_frames):]
+        if self.cur_ref_idc:   # sliding-window or adaptive marking (8.2.5); IDR empties the DPB first
+            lt_flag, mmco = self.cur_marking
+            self.marking.mark(RefFrame(self.cur_frame_num, (y.copy(), u.copy(), v.copy())), self.cur_idr,
+                              1 << sps.log2_max_frame_num, sps.max_num_ref_frames, mmco, lt_flag)
         self.cur = None
 
     # -------------------------------------------------------------------
@@ -468,17 +600,38 @@ class H264Decoder:
         if slice_type not in (0, 2):
             raise NotImplementedError(f"slice_type {slice_type}")
         num_ref = pps.num_ref_idx_l0
+        mods: list = []
         if slice_type == 0:
             if br.u1():
                 num_ref = br.ue() + 1
-            if br.u1():
-                raise NotImplementedError("ref_pic_list_modification")
-        if ref_idc:
+            if br.u1():   # ref_pic_list_modification_flag_l0 (7.3.3.1)
+                while True:
+                    idc = br.ue()
+                    if idc == 3:
+                        break
+                    if idc > 3:
+                        raise BitstreamError("modification_of_pic_nums_idc out of range")
+                    mods.append((idc, br.ue()))
+        marking = (False, None)
+        if ref_idc:   # dec_ref_pic_marking() (7.3.3.3)
             if idr:
                 br.u1()
-                br.u1()
+                marking = (bool(br.u1()), None)
             elif br.u1():
-                raise NotImplementedError("adaptive_ref_pic_marking")
+                ops = []
+                while True:
+                    op = br.ue()
+                    if op == 0:
+                        break
+                    if op in (1, 2, 4, 6):
+                        ops.append((op, br.ue()))
+                    elif op == 3:
+                        ops.append((op, br.ue(), br.ue()))
+                    elif op == 5:
+                        raise NotImplementedError("memory_management_control_operation 5")
+                    else:
+                        raise BitstreamError("memory_management_control_operation out of range")
+                marking = (False, tuple(ops))
         qp = pps.pic_init_qp + br.se()
         db = (0, 0, 0)
         if pps.deblocking_filter_control_present:
@@ -496,14 +649,20 @@ class H264Decoder:
             self.cur_frame_num = frame_num
             self.cur_ref_idc = ref_idc
             self.cur_idr = idr
+            self.cur_marking = marking
             self.cur = (np.zeros((sps.mb_h * 16, sps.mb_w * 16), np.uint8),
                         np.zeros((sps.mb_h * 8, sps.mb_w * 8), np.uint8),
                         np.zeros((sps.mb_h * 8, sps.mb_w * 8), np.uint8))
             self.mbs = [MbState() for _ in range(sps.mb_w * sps.mb_h)]
             if idr:
                 self.stats["idr"] += 1
-        if slice_type == 0 and not self.dpb:
-            raise BitstreamError("P slice without a reference picture")
+        elif marking != self.cur_marking:
+            raise BitstreamError("the slices of one picture disagree on dec_ref_pic_marking()")
+        if slice_type == 0:
+            frames = self.marking.build_list(frame_num, 1 << sps.log2_max_frame_num, num_ref, mods)
+            self.ref_list = [f.planes if f is not None else None for f in frames]
+            if not self.ref_list or self.ref_list[0] is None:
+                raise BitstreamError("P slice without a reference picture")
         self.slice_counter += 1
         self.stats["slices"] += 1
         self.cur_pps = pps
@@ -1199,9 +1358,9 @@ class H264Decoder:
 
     # ---- motion compensation (8.4.2.2) ------------------------------------------
     def _mc(self, sps, mbx, mby, mvx, mvy, write=True, ref_idx=0):
-        if ref_idx >= len(self.dpb):
-            raise BitstreamError(f"ref_idx {ref_idx} with {len(self.dpb)} reference pictures")
-        rY, rU, rV = self.dpb[ref_idx]
+        if ref_idx >= len(self.ref_list) or self.ref_list[ref_idx] is None:
+            raise BitstreamError(f"ref_idx {ref_idx}: no reference picture at that list position")
+        rY, rU, rV = self.ref_list[ref_idx]
         H, W = rY.shape
         x0, y0 = mbx * 16, mby * 16
         xi, yi = x0 + (mvx >> 2), y0 + (mvy >> 2)

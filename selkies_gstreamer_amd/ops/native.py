@@ -35,7 +35,7 @@ class SkH264Config(ctypes.Structure):
         ("num_refs", ctypes.c_int32), ("codec", ctypes.c_int32), ("aq_strength", ctypes.c_int32),
         ("subpel", ctypes.c_int32), ("intra4x4", ctypes.c_int32),
         ("tile_cols_log2", ctypes.c_int32), ("tile_rows_log2", ctypes.c_int32),
-        ("rc_mode", ctypes.c_int32), ("bitrate_kbps", ctypes.c_int32),
+        ("rc_mode", ctypes.c_int32), ("bitrate_kbps", ctypes.c_int32), ("ltr_slots", ctypes.c_int32),
     ]
 
 
@@ -69,7 +69,7 @@ class SkCaptureSettings(ctypes.Structure):
         ("pool_frames", ctypes.c_int32), ("pool_stride", ctypes.c_int32), ("pool_phase", ctypes.c_int32),
         ("h264_aq_strength", ctypes.c_int32), ("h264_subpel", ctypes.c_int32), ("h264_intra4x4", ctypes.c_int32),
         ("h264_rc_mode", ctypes.c_int32), ("h264_bitrate_kbps", ctypes.c_int32),
-        ("h264_me_full", ctypes.c_int32),
+        ("h264_me_full", ctypes.c_int32), ("h264_ltr_slots", ctypes.c_int32),
     ]
 
 
@@ -305,6 +305,11 @@ ME_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<i4"), ("intra_est
 TASK_DTYPE = np.dtype([(n, "<i4") for n in (
     "action", "qp", "first_row", "num_rows", "pic_row0", "pic_rows", "frame_num", "idr_pic_id",
     "allow_scenecut", "idr_on_intra", "final_action", "num_refs")])
+# Long-term reference cache (csrc/codec/ltr.h): per-stream state and per-slice decisions
+LTR_STATE_DTYPE = np.dtype([("quiet_run", "<i4"), ("cur_slot", "<i4"), ("clock", "<i4"), ("valid", "<i4"),
+                            ("stamp", "<i4", (8,)), ("n_st", "<i4"), ("st_fn", "<i4", (9,)), ("pad", "<i4", (2,))])
+LTR_TASK_DTYPE = np.dtype([("slot", "<i4"), ("store_slot", "<i4"), ("mmco1", "<i4"), ("flags", "<i4"),
+                           ("ref1_mbs", "<i4"), ("pad", "<i4", (3,))])
 
 
 RC_MODES = {"cqp": 0, "crf": 1, "cbr": 2}
@@ -335,8 +340,10 @@ class H264Encoder:
                  src_width: int = 0, src_height: int = 0, num_refs: int = 1, codec: str = "h264",
                  aq_strength: float = 0.0, subpel: bool = True, intra4x4: bool = False,
                  tile_cols_log2: int = -1, tile_rows_log2: int = -1, rate_control: str = "cqp",
-                 bitrate_kbps: int = 0):
-        """aq_strength: MB-level adaptive QP (h264_mb.h aq_offset), 1.0 = x264 aq-mode 1
+                 bitrate_kbps: int = 0, ltr_slots: int = 0):
+        """ltr_slots: H.264 long-term reference cache, pictures kept per stream (stripe, or the
+        picture in full-frame mode) for content that comes back, 0 = off, 1..8; not with
+        num_refs > 1. aq_strength: MB-level adaptive QP (h264_mb.h aq_offset), 1.0 = x264 aq-mode 1
         strength; 0 = constant QP per slice (x264 ultrafast behaviour). deblock: True / False,
         or "auto" (the slices coded at QP >= 34, h264_encoder.h slice_deblock)."""
         L = lib()
@@ -352,7 +359,7 @@ class H264Encoder:
                                 int(num_refs), {"h264": 0, "hevc": 1, "av1": 2}.get(codec, 0),
                                 int(round(aq_strength * 16)), 0 if subpel else -1, 1 if intra4x4 else 0,
                                 int(tile_cols_log2), int(tile_rows_log2),
-                                RC_MODES[rate_control], int(bitrate_kbps))
+                                RC_MODES[rate_control], int(bitrate_kbps), int(ltr_slots))
         if codec not in ("h264", "hevc", "av1"):
             raise ValueError("codec must be 'h264', 'hevc' or 'av1'")
         self.codec = codec
