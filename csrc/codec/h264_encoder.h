@@ -171,6 +171,21 @@ SK_HD bool rc_slice_adjustable(const SliceTask& t, int plan_qp, int mode = 1) {
     return (t.final_action == ACT_P || t.final_action == ACT_I) && (t.qp == plan_qp || mode == 2);
 }
 
+// Upper bound of the slice QPs (SliceTask::qp) of a frame that is planned under rate mode
+// `mode` with QP `qp` and paint-over QP `paint_qp` (the configured values or their set_qp
+// overrides, whichever apply to that frame). plan_stripe gives every slice one of the
+// two. CQP: rc_apply leaves them. CRF: a slice at `qp` moves to rc_clamp_qp of
+// rc_frame_qpf's base_qp + [-3, +6] (base_qp is `qp`; a whole QP, so rc_dither_qp adds
+// nothing; H.264's qp_min can lift it), a paint-over slice keeps paint_qp. CBR: the
+// controller and the guard's second pass (rc_redo) reach every QP up to 51, so no bound
+// below that holds: 51. The HIP back end leaves its deblocking kernels out of a frame
+// whose bound is below kAutoDeblockQp (deblock = 2).
+SK_HD int max_slice_qp(int mode, int qp, int paint_qp) {
+    if (mode == RC_CQP) return sk_max(qp, paint_qp);
+    if (mode == RC_CRF) return sk_max(sk_clip(qp + 6, rc_qp_min_for(0), 51), paint_qp);
+    return 51;
+}
+
 struct StripeState {
     int frame_num = 0;     // next frame_num
     int idr_pic_id = 0;

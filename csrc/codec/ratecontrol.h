@@ -1,5 +1,5 @@
 // K10 rate control, shared by the CPU reference controller and the GPU one
-// (k_rc_qp after the motion search, k_ep_count / k_rc_account after the bitstream), so both
+// (k_rc_qp after the motion search, k_commit / k_rc_account after the bitstream), so both
 // backends choose the same QP for the same frame.
 //
 // Modes (reference parity):

@@ -12,6 +12,7 @@ namespace gpu {
 
 constexpr int kMbSlotBytes = 1024;     // per-MB CAVLC bit buffer (A.3.1 caps a MB at 400 B)
 constexpr int kSliceHdrMax = 64;       // SPS+PPS+stripe header prefix room per slot
+constexpr int kPackMaxSliceMbs = 16384;   // k_slice_pack: macroblocks of one slice (16 MB rows of an 8K picture: 8192)
 
 struct Planes {
     uint8_t* y;
@@ -43,13 +44,7 @@ struct FrameArgs {
     int16_t* coefs;        // [num_mbs][kCoefPerMb]
     uint32_t* mb_bits;     // [num_mbs][kMbSlotBytes/4]
     int* mb_nbits;         // [num_mbs]
-    uint32_t* rbsp;        // [num_slices][rbsp_slot_words] (self-cleaning)
-    int rbsp_slot_words;
-    int* mb_off;           // [num_mbs] bit offset of each MB inside its slice RBSP
-    int* slice_info;       // [num_slices * nal_per_slice][4]: RBSP bytes, packet prefix bytes
-    int* tile_carry;       // [num_slices * nal_per_slice][max_tiles] last non-zero RBSP byte before each EP tile (-1: none)
-    int* tile_ins;         // [num_slices * nal_per_slice][max_tiles] emulation-prevention insertions per tile
-    int max_tiles;
+    int* slice_info;       // [num_slices * nal_per_slice][4]: RBSP bytes, packet prefix bytes (k_slice_pack)
     int out_slot_bytes;    // bytes per slice slot in host_out
     const uint8_t* param_sets;  // [num_slices or 1][kParamSetMax]
     const int* param_set_len;
@@ -77,11 +72,9 @@ struct FrameArgs {
     long long* rc_slice;   // [num_slices][2] complexity sums of P-planned slices (SAD, activity)
     float rc_fps;          // session frame rate (CBR frame budget)
     int* rc_redo;          // K10 CBR guard: device flag, 1 = code the frame again (k_rc_guard)
-    // K5 sub-slices (h264_encoder.h intra_split): NAL slots per slice. slice_info / tile_carry /
-    // tile_ins are indexed by NAL (slice * nal_per_slice + sub-slice); sub-slice j's RBSP
-    // starts at word j * sub_rbsp_words of its slice's rbsp slot.
+    // K5 sub-slices (h264_encoder.h intra_split): NAL slots per slice. slice_info is indexed
+    // by NAL (slice * nal_per_slice + sub-slice).
     int nal_per_slice;
-    int sub_rbsp_words;
     const int* gate;       // second-pass launches: run only when *gate != 0 (null: always)
     // planar 4:2:0 input (YuvInput, h264_frame.h) staged on the device: W x H luma (pitch
     // W), then I420 U and V ((W+1)/2 x (H+1)/2 each) or NV12 interleaved UV (pitch
@@ -108,7 +101,12 @@ void launch_convert_damage(const FrameArgs& a, hipStream_t s);
 void launch_encode(const FrameArgs& a, hipStream_t s, bool guard = false);
 // k_plan, motion search and scene-cut decisions only (the HEVC back end follows it)
 void launch_frontend(const FrameArgs& a, hipStream_t s);
-void launch_commit(const FrameArgs& a, hipStream_t s);   // MV field + reference update (+ K7 deblocking)
+// MV field + reference update (+ K7 deblocking). filter = false leaves the three deblocking
+// kernels out: for frames in which no slice can be filtered (slice_deblock false for every
+// slice, see max_slice_qp in h264_encoder.h), where they would only exit.
+// account: the H.264 chain's K10 accounting (the NAL sizes k_slice_pack left in slice_info)
+// runs in the first workgroup of k_commit; the HEVC / AV1 back ends use launch_rc_account.
+void launch_commit(const FrameArgs& a, hipStream_t s, bool filter = true, bool account = false);
 // K10 accounting of the frame just coded: frame bytes = sum of sizes[i * stride],
 // i < n (per_slice: only slices that were coded).
 void launch_rc_account(const FrameArgs& a, const int* sizes, int n, int stride, int per_slice, hipStream_t s);

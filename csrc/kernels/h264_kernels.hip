@@ -16,14 +16,16 @@
 //   k_decide                 per-slice scene-cut decision
 //   k_rc_qp           K10    frame QP: one lane's serial chain, on LDS copies of its inputs
 //   k_code_inter      K6     MC, transform, quant/decimation, QP escalation, recon
-//   k_code_intra      K5+K6  Intra16x16 wavefront (one wave per MB row, lag 2)
+//   k_code_intra      K5+K6  Intra16x16 wavefront (one wave per MB row, lag 2); where I slices are
+//                            sub-sliced (mb_w > kIntraSubMbs) k_code_intra_sub is launched instead
 //   k_cavlc           K8     per-MB CAVLC: lanes code residual blocks in parallel,
 //                            bit offsets by wave prefix-sum, LDS atomicOr packing
-//   k_slice_scan, k_mb_concat, k_ep_count, k_ep_write   K9  slice header + MB offsets, MB bit
-//                            concatenation, tile-parallel emulation prevention
+//   k_slice_pack      K9     one workgroup per slice: slice header, scan of the MB bit counts, MB
+//                            bit concatenation and emulation prevention in LDS, 16-byte stores
 //                            straight into host-mapped packet slots
-//   k_commit                 MV-field update (+ plain reference copy when K7 is off)
-//   k_deblock_prep, k_deblock  K7  in-loop deblocking rec -> ref (LDS-ring wavefront)
+//   k_commit                 MV-field update (+ plain reference copy when K7 is off), K10 accounting
+//   k_deblock_prep, k_deblock_edges, k_deblock  K7  in-loop deblocking rec -> ref (LDS-ring
+//                            wavefront); not launched for a frame in which no slice can be filtered
 #include "h264_gpu.h"
 #include "../codec/color.h"
 #include "../codec/h264_mb.h"
@@ -70,10 +72,6 @@ __device__ __forceinline__ bool split_i(const FrameArgs& a, const SliceTask& t) 
 __device__ __forceinline__ int slice_nals(const FrameArgs& a, const SliceTask& t) {
     if (t.final_action == ACT_NONE) return 0;
     return split_i(a, t) ? intra_sub_count(t.num_rows * a.mb_w) : 1;
-}
-// RBSP of NAL j of slice s
-__device__ __forceinline__ uint32_t* nal_rbsp(const FrameArgs& a, int s, int j) {
-    return a.rbsp + (size_t)s * a.rbsp_slot_words + (size_t)j * a.sub_rbsp_words;
 }
 
 __device__ __forceinline__ int wave_incl_scan_max(int v) {
@@ -253,7 +251,7 @@ struct StageBitWriter {
 // host-mapped memory (no same-line atomics, no device->host copy).
 //
 // The host-mapped words of the frame (keyframe / QP / rate snapshot for k_plan and k_rc_qp,
-// frame id for k_slice_scan) are fetched by the first workgroup of the damage kernel: ten
+// frame id for k_slice_pack) are fetched by the first workgroup of the damage kernel: ten
 // lanes, one PCIe round trip that completes while the workgroup converts, stored to device
 // memory at its end. k_plan, a single workgroup on the frame's critical path, then reads
 // device memory only.
@@ -1098,18 +1096,15 @@ __device__ __forceinline__ void rc_account_wave(const FrameArgs& a, const int* s
     if (lane_id() == 0) rc_account(*a.rc, 8 * b);
 }
 
-// K10 accounting of the HEVC / AV1 back ends (the H.264 chain does it in k_ep_count)
+// K10 accounting of the HEVC / AV1 back ends (the H.264 chain does it in k_commit)
 __global__ __launch_bounds__(64) void k_rc_account(FrameArgs a, const int* sizes, int n, int stride, int per_slice) {
     rc_account_wave(a, sizes, n, stride, per_slice);
 }
 
-// K10 CBR guard after k_slice_scan, one workgroup: the overflow test on the frame's
-// payload; on a redo it moves the slice QPs (rc_redo) and raises the flag for the gated
-// second pass, whose k_slice_scan first clears the header / trailing bits the first one
-// left in its RBSP slot. (Clearing here, per slice, from a test every workgroup repeated,
-// went wrong in two ways: a step that rc_redo does not apply - the frame already at the
-// top QP - cleared slots that no second pass filled again, and a workgroup that evaluated
-// the step after rc_redo had counted the pass saw none and kept its stale bits.)
+// K10 CBR guard after the size-only k_slice_pack, one workgroup: the overflow test on the
+// frame's payload; on a redo it moves the slice QPs (rc_redo) and raises the flag for the
+// gated second coding pass. Nothing of the first pass is packed: the full k_slice_pack
+// runs once, behind whichever pass coded the frame last.
 __global__ __launch_bounds__(256) void k_rc_guard(FrameArgs a) {
     __shared__ long long part[4];
     const int tid = threadIdx.x;
@@ -2792,356 +2787,348 @@ __global__ __launch_bounds__(256) void k_cavlc(FrameArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// K9: slice assembly (one 256-thread workgroup per coded slice).
-// ---------------------------------------------------------------------------
-// K9: slice assembly, tile-parallel.
-//   k_slice_scan  one workgroup per slice: slice header, exclusive scan of the MB
-//                 bit counts -> per-MB bit offsets, trailing mb_skip_run + stop
-//                 bit, packet prefix (stripe header, SPS/PPS on IDR, start code,
-//                 NAL header) written straight into the host-mapped slot
-//   k_mb_concat   one wave per MB: shifts its CAVLC words into the slice RBSP
-//                 (plain stores; atomicOr only on the two edge words it shares)
-//   k_ep_count / k_ep_write   4 KiB tiles of every slice in parallel:
-//                 emulation prevention (7.4.1) — a 0x03 goes before byte i iff
-//                 b_i <= 3 and the zero run z(i) right before i is even and >= 2,
-//                 which only depends on the input bytes; a tile needs the last
-//                 non-zero byte before it (its carry: k_ep_count looks backwards
-//                 from the tile, codec/h264_ep.h) and the number of insertions
-//                 before it (prefix sum of k_ep_count). k_ep_write stages its
-//                 output in LDS, streams it to host memory with 16-byte stores and
-//                 self-cleans the RBSP words it consumed. k_ep_count also does the
-//                 frame's K10 accounting (one wave of its first workgroup).
-constexpr int kTile = 4096;
+// K9: slice assembly, k_slice_pack: one workgroup per slice does all of it in LDS.
+// Every dependency of the bitstream tail lies inside one slice (the scan of the MB bit
+// counts, the emulation-prevention carry, the insertions before a byte, the slot offset
+// of a sub-NAL behind its predecessors), so nothing is handed from one workgroup to
+// another and no RBSP goes through device memory. The workgroup walks the slice's NALs
+// in order (one, or the sub-slices of a split I slice). Per NAL:
+//   - slice header into LDS (one lane), packet prefix (stripe header, SPS/PPS on IDR,
+//     start code, NAL header) straight into the host-mapped slot
+//   - MB bit counts summed per batch of kPackThreads MBs, last coded MB, trailing
+//     mb_skip_run + stop bit -> the NAL's size (slice_info)
+//   - per chunk of kPackChunk RBSP bytes: the bit offsets of the batches that reach into
+//     the chunk go to LDS (batch 0's are kept in registers from the size pass), and the
+//     chunk is filled word-parallel: a thread owns kPackWordsPerThread words, finds the MBs that put bits
+//     into each by binary search over the offsets and shifts their CAVLC words together
+//     (one round of loads in flight for the whole chunk, whatever the MB sizes; no atomics;
+//     a MB that straddles a chunk boundary contributes to both chunks) - then emulation prevention
+//     (7.4.1, codec/h264_ep.h ep_lane: kEpLaneBytes bytes per lane, the last non-zero
+//     byte index carried from chunk to chunk in a register) into an LDS stage, which is
+//     streamed to the slot with 16-byte stores at the running offset.
+// kSizeOnly (CBR guard, ahead of k_rc_guard): sizes only - no chunk is built and nothing
+// is written to the host. K10 accounting needs every NAL's size: k_commit does it.
+// 512 threads, 8 KiB chunks: a footprint that finds room between the other sessions'
+// workgroups (the larger shapes that were measured: profiles/h264_pack_kernels.md).
+constexpr int kPackThreads = 512;
+constexpr int kPackChunk = kPackThreads * kEpLaneBytes;
+constexpr int kPackWords = kPackChunk / 4;
+constexpr int kPackWordsPerThread = kPackWords / kPackThreads;
+constexpr int kPackMaxBatches = kPackMaxSliceMbs / kPackThreads;
+static_assert(kPackMaxSliceMbs % kPackThreads == 0, "whole batches");
 
-__global__ __launch_bounds__(256) void k_slice_scan(FrameArgs a) {
-    if (a.gate && *a.gate == 0) return;   // CBR second pass not needed
+// 32 bits of a run of nb bits (src words, most significant bit first) from its bit sb on.
+// sb may be negative: the run then starts inside the word. Zeros outside [0, nb).
+__device__ __forceinline__ uint32_t pack_bits32(const uint32_t* src, int nb, int sb) {
+    if (sb <= -32 || sb >= nb) return 0u;
+    const int nw = (nb + 31) >> 5, k = sb >> 5, r = sb & 31;   // k = -1 for a negative sb
+    const uint32_t lastmask = (nb & 31) ? ~0u << (32 - (nb & 31)) : ~0u;
+    uint32_t x = 0u, y = 0u;
+    if (k >= 0) {
+        x = src[k];
+        if (k == nw - 1) x &= lastmask;
+    }
+    if (r && k + 1 < nw) {
+        y = src[k + 1];
+        if (k + 1 == nw - 1) y &= lastmask;
+    }
+    return r ? (x << r) | (y >> (32 - r)) : x;
+}
+
+// First index m < kPackThreads with e[m] > x (e non-decreasing), kPackThreads if none.
+__device__ __forceinline__ int pack_upper_bound(const int* e, int x) {
+    int lo = 0;
+#pragma unroll
+    for (int step = kPackThreads / 2; step > 0; step >>= 1)
+        if (e[lo + step - 1] <= x) lo += step;
+    return e[lo] <= x ? lo + 1 : lo;
+}
+
+template <bool kSizeOnly>
+__global__ __launch_bounds__(kPackThreads) void k_slice_pack(FrameArgs a) {
+    constexpr int NW = kPackThreads / 64;
+    // One LDS block, used twice per chunk: first the RBSP chunk and, behind it, the bit range
+    // of each MB of a batch (s_off, s_end); then, once every thread holds its chunk bytes in
+    // registers, the emulation-prevention output stage (3/2 of the chunk at its worst).
+    constexpr int kStage = kPackChunk + kPackChunk / 2 + 16, kFill = kPackChunk + 8 * kPackThreads;
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kSizeOnly ? 16 : (kStage > kFill ? kStage : kFill)];
+    uint32_t* chunk = reinterpret_cast<uint32_t*>(lds);
+    int* s_off = reinterpret_cast<int*>(lds + (kSizeOnly ? 0 : kPackChunk));
+    int* s_end = s_off + (kSizeOnly ? 0 : kPackThreads);
+    uint8_t* sOut = lds;
     __shared__ uint32_t hdr[32];
-    __shared__ int wave_tot[5];
-    __shared__ int sh_misc[4];
-    // one workgroup per NAL slot: slice s, sub-slice j (K5; j = 0 is the whole slice otherwise)
-    const int nal = blockIdx.x, s = nal / a.nal_per_slice, j = nal % a.nal_per_slice, tid = threadIdx.x;
+    __shared__ uint32_t tail[4];
+    __shared__ int wave_tot[NW + 1];
+    __shared__ int scan_lds[NW];
+    __shared__ int bbase[kPackMaxBatches + 1];   // bits of the MBs before each batch
+    __shared__ int sh_misc[4];                   // [0] header bits, [1] last coded MB, [2] trailing bits
+    const int s = blockIdx.x, tid = threadIdx.x;
     const SliceTask task = a.tasks[s];
     const int fin = task.final_action;
-    int* info = a.slice_info + 4 * nal;
     const int nn = slice_nals(a, task);
-    if (a.gate && info[0] > 0) {
-        // second pass: the first one's header and trailing bits are still in this NAL's RBSP
-        // (its size is in info[0]; the NALs of a slice are the same in both passes)
-        uint32_t* old = nal_rbsp(a, s, j);
-        const int words = (info[0] + 3) / 4 + 1;
-        for (int i = tid; i < words; i += 256) old[i] = 0u;
-        __syncthreads();
+    for (int j = nn + tid; j < a.nal_per_slice; j += kPackThreads) {   // NAL slots this frame leaves empty
+        int* info = a.slice_info + 4 * (s * a.nal_per_slice + j);
+        info[0] = 0;
+        info[1] = 0;
     }
-    if (j >= nn) {
-        if (tid == 0) {
-            info[0] = 0;
-            info[1] = 0;
-            if (j == 0) a.host_size[s] = 0;
-        }
+    if (nn == 0) {
+        if (!kSizeOnly && tid == 0) a.host_size[s] = 0;
         return;
     }
     const int snmb = task.num_rows * a.mb_w;
-    const int k0 = nn > 1 ? j * kIntraSubMbs : 0;
-    const int nmb = nn > 1 ? sk_min(snmb, k0 + kIntraSubMbs) - k0 : snmb;
-    const int first = task.first_row * a.mb_w + k0;
-    uint32_t* rbsp = nal_rbsp(a, s, j);
     const bool intra = fin == ACT_I;
     const bool idr = intra && task.idr_on_intra;
-    if (tid < 32) hdr[tid] = 0;
-    if (tid == 0) sh_misc[1] = -1;
-    __syncthreads();
-    if (tid == 0) {
-        AtomicBitWriter w{hdr, 0};
-        SliceHeaderParams h;
-        h.first_mb = (a.fullframe ? task.first_row * a.mb_w : 0) + k0;
-        h.slice_type = intra ? 2 : 0;
-        h.idr = idr;
-        h.frame_num = idr ? 0 : task.frame_num;
-        h.idr_pic_id = task.idr_pic_id;
-        h.slice_qp = task.qp;
-        h.deblock = slice_deblock(a.deblock, task);
-        h.num_refs = intra ? 1 : task.num_refs;
-        if (a.ltr_slots) {   // long-term cache: list modification / marking, as the CPU writer
-            const ltr::LtrTask L = a.ltr_task[s];
-            if (fin == ACT_P) h.lt_ref = L.slot;
-            if (!idr && L.store_slot >= 0) {
-                h.lt_store = L.store_slot;
-                h.lt_max_idx = a.ltr_slots;
-                h.st_drop = L.mmco1;
+    uint8_t* dst = a.host_out + (size_t)s * a.out_slot_bytes;
+    // loaded ahead of their use (wave-uniform): every dependent round trip to device memory
+    // counts in a chain that one workgroup walks alone
+    const int fid = a.frame_params_dev[0];
+    const int ps_len = a.param_set_len[s];
+    int slot_pos = 0;   // bytes of this slice's slot written so far
+    // Bit count of this thread's MB in batch 0 of NAL jj. The next NAL's is loaded while this one
+    // is packed: the sub-NALs of a key frame's slice would otherwise each start with a round trip.
+    auto batch0_bits = [&](int jj) -> int {
+        const int k0 = nn > 1 ? jj * kIntraSubMbs : 0;
+        const int nmb = nn > 1 ? sk_min(snmb, k0 + kIntraSubMbs) - k0 : snmb;
+        return (fin != ACT_SKIPALL && tid < nmb) ? a.mb_nbits[task.first_row * a.mb_w + k0 + tid] : 0;
+    };
+    int nb_ahead = batch0_bits(0);
+    for (int j = 0; j < nn; j++) {
+        const int nb_first = nb_ahead;
+        if (j + 1 < nn) nb_ahead = batch0_bits(j + 1);
+        int* info = a.slice_info + 4 * (s * a.nal_per_slice + j);
+        const int k0 = nn > 1 ? j * kIntraSubMbs : 0;
+        const int nmb = nn > 1 ? sk_min(snmb, k0 + kIntraSubMbs) - k0 : snmb;
+        const int first = task.first_row * a.mb_w + k0;
+        if (tid < 32) hdr[tid] = 0;
+        if (tid < 4) tail[tid] = 0;
+        if (tid == 0) sh_misc[1] = -1;
+        __syncthreads();
+        if (tid == 0) {
+            AtomicBitWriter w{hdr, 0};
+            SliceHeaderParams h;
+            h.first_mb = (a.fullframe ? task.first_row * a.mb_w : 0) + k0;
+            h.slice_type = intra ? 2 : 0;
+            h.idr = idr;
+            h.frame_num = idr ? 0 : task.frame_num;
+            h.idr_pic_id = task.idr_pic_id;
+            h.slice_qp = task.qp;
+            h.deblock = slice_deblock(a.deblock, task);
+            h.num_refs = intra ? 1 : task.num_refs;
+            if (a.ltr_slots) {   // long-term cache: list modification / marking, as the CPU writer
+                const ltr::LtrTask L = a.ltr_task[s];
+                if (fin == ACT_P) h.lt_ref = L.slot;
+                if (!idr && L.store_slot >= 0) {
+                    h.lt_store = L.store_slot;
+                    h.lt_max_idx = a.ltr_slots;
+                    h.st_drop = L.mmco1;
+                }
             }
+            write_slice_header(w, h);
+            if (fin == ACT_SKIPALL) put_ue(w, (uint32_t)nmb);
+            sh_misc[0] = (int)w.pos;
         }
-        write_slice_header(w, h);
-        if (fin == ACT_SKIPALL) put_ue(w, (uint32_t)nmb);
-        sh_misc[0] = (int)w.pos;
-    }
-    const int per = (nmb + 255) / 256;
-    const int m0 = sk_min(nmb, tid * per), m1 = sk_min(nmb, m0 + per);
-    int local = 0, last_coded = -1;
-    if (fin != ACT_SKIPALL)
-        for (int m = m0; m < m1; m++) {
-            const int nb = a.mb_nbits[first + m];
-            local += nb;
-            if (nb > 0) last_coded = m;
+        // MB bits per batch of kPackThreads MBs, last coded MB
+        const int nbatch = (nmb + kPackThreads - 1) / kPackThreads;
+        int total = 0, nb0 = 0, ex0 = 0;   // batch 0's count and offset stay in registers for the packing
+        for (int b = 0; b < nbatch; b++) {
+            const int m = b * kPackThreads + tid;
+            const int nb = b == 0 ? nb_first : ((fin != ACT_SKIPALL && m < nmb) ? a.mb_nbits[first + m] : 0);
+            const int lc = wave_incl_scan_max(nb > 0 ? m : -1);
+            if (lane_id() == 63 && lc >= 0) atomicMax(&sh_misc[1], lc);
+            int bt;
+            const int ex = block_excl_scan<NW>(nb, wave_tot, &bt);
+            if (b == 0) {
+                nb0 = nb;
+                ex0 = ex;
+            }
+            if (tid == 0) bbase[b] = total;
+            total += bt;
         }
-    if (last_coded >= 0) atomicMax(&sh_misc[1], last_coded);
-    int total;
-    const int excl = block_excl_scan<4>(local, wave_tot, &total);
-    const int hb = sh_misc[0];
-    if (fin != ACT_SKIPALL) {
-        int off = hb + excl;
-        for (int m = m0; m < m1; m++) {
-            a.mb_off[first + m] = off;
-            off += a.mb_nbits[first + m];
+        if (tid == 0) bbase[nbatch] = total;
+        __syncthreads();
+        const int hb = sh_misc[0];
+        if (tid == 0) {
+            AtomicBitWriter w{tail, 0};
+            if (fin == ACT_P) {
+                const int trailing = nmb - 1 - sh_misc[1];
+                if (trailing > 0) put_ue(w, (uint32_t)trailing);
+            }
+            w.put(1, 1);  // rbsp_stop_one_bit
+            sh_misc[2] = (int)w.pos;
         }
-    }
-    if (tid < 32 && tid * 32 < hb) atomicOr(&rbsp[tid], hdr[tid]);  // last header word is shared with MB 0
-    if (tid == 0) {
-        AtomicBitWriter w{rbsp, (uint32_t)(hb + total)};
-        if (fin == ACT_P) {
-            const int trailing = nmb - 1 - sh_misc[1];
-            if (trailing > 0) put_ue(w, (uint32_t)trailing);
+        __syncthreads();
+        const int tb = sh_misc[2];
+        const int n = (hb + total + tb + 7) >> 3;   // RBSP bytes
+        // bytes ahead of the RBSP: start code + NAL header, behind the stripe header and the
+        // parameter sets for the first NAL of a stripe's packet
+        const int prefix = (j == 0 && !a.fullframe) ? 15 + (idr ? ps_len : 0) : 5;
+        if (tid == 0) {
+            info[0] = n;
+            info[1] = prefix;
         }
-        w.put(1, 1);  // rbsp_stop_one_bit
-        info[0] = (int)((w.pos + 7) >> 3);
-        if (j > 0) {   // start code + NAL header: written by k_ep_write once the NALs before it are sized
-            info[1] = 5;
-        } else {       // packet prefix, written directly into the host-mapped slot
-            uint8_t* slot = a.host_out + (size_t)s * a.out_slot_bytes;
-            int p = 0;
-            if (!a.fullframe) {
+        if (kSizeOnly) continue;
+        if (tid == 0) {
+            int p = slot_pos;
+            if (j == 0 && !a.fullframe) {
                 const int y = task.first_row * 16;
                 const int h = sk_min(a.H, (task.first_row + task.num_rows) * 16) - y;
-                const int fid = a.frame_params_dev[0];
                 uint8_t pre[10] = {0x04, (uint8_t)(idr ? 1 : 0), (uint8_t)(fid >> 8), (uint8_t)fid, (uint8_t)(y >> 8),
                                    (uint8_t)y, (uint8_t)(a.W >> 8), (uint8_t)a.W, (uint8_t)(h >> 8), (uint8_t)h};
-                for (int i = 0; i < 10; i++) slot[i] = pre[i];
+                for (int i = 0; i < 10; i++) dst[i] = pre[i];
                 p = 10;
                 if (idr) {
-                    const int len = a.param_set_len[s];
+                    const int len = ps_len;
                     const uint8_t* ps = a.param_sets + (size_t)s * a.param_set_stride;
-                    for (int i = 0; i < len; i++) slot[p + i] = ps[i];
+                    for (int i = 0; i < len; i++) dst[p + i] = ps[i];
                     p += len;
                 }
             }
-            slot[p++] = 0; slot[p++] = 0; slot[p++] = 0; slot[p++] = 1;
-            slot[p++] = idr ? 0x65 : 0x41;
-            info[1] = p;
+            dst[p] = 0; dst[p + 1] = 0; dst[p + 2] = 0; dst[p + 3] = 1;
+            dst[p + 4] = idr ? 0x65 : 0x41;
         }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mb_concat(FrameArgs a) {
-    const int w = threadIdx.x >> 6, l = lane_id();
-    const int mb = blockIdx.x * 4 + w;
-    if (mb >= a.mb_w * a.mb_h) return;
-    const int s = (mb / a.mb_w) / a.rows_per_slice;
-    const SliceTask& task = a.tasks[s];
-    const int fin = task.final_action;
-    if (fin == ACT_NONE || fin == ACT_SKIPALL) return;
-    const int nb = a.mb_nbits[mb];
-    if (nb <= 0) return;
-    const int sub = split_i(a, task) ? (mb - task.first_row * a.mb_w) / kIntraSubMbs : 0;   // K5 NAL of the MB
-    const int p = a.mb_off[mb];
-    const int w0 = p >> 5, w1 = (p + nb - 1) >> 5, sh = p & 31;
-    const int nw = (nb + 31) >> 5;
-    const uint32_t lastmask = (nb & 31) ? ~0u << (32 - (nb & 31)) : ~0u;
-    const uint32_t* src = a.mb_bits + (size_t)mb * (kMbSlotBytes / 4);
-    uint32_t* dst = nal_rbsp(a, s, sub);
-    for (int j = w0 + l; j <= w1; j += 64) {
-        const int k = j - w0;
-        uint32_t lo = k < nw ? src[k] : 0u;
-        if (k == nw - 1) lo &= lastmask;
-        uint32_t v;
-        if (sh == 0) {
-            v = lo;
-        } else {
-            uint32_t hi = 0u;
-            if (k >= 1) {
-                hi = src[k - 1];
-                if (k - 1 == nw - 1) hi &= lastmask;
+        int out_pos = slot_pos + prefix;
+        int carry = -1;   // EpState::last_nz: last non-zero RBSP byte of the chunks before
+        const int nchunks = (n + kPackChunk - 1) / kPackChunk;
+        for (int c = 0; c < nchunks; c++) {
+            const int cb = c * kPackChunk, clen = sk_min(kPackChunk, n - cb), cw0 = c * kPackWords;
+            const long long bit0 = 8ll * cb, bit1 = bit0 + 8ll * kPackChunk;
+            for (int i = tid; i < ((clen + 3) >> 2); i += kPackThreads) chunk[i] = 0u;
+            __syncthreads();
+            // Every word of the chunk has one owner per phase (header, each batch of MBs,
+            // trailing bits; barriers between them), so plain read-modify-writes do.
+            if (c == 0 && tid < 32 && tid * 32 < hb) chunk[tid] |= hdr[tid];
+            for (int b = 0; b < nbatch; b++) {
+                const int bb0 = hb + bbase[b], bb1 = hb + bbase[b + 1];
+                if (bb1 == bb0 || bb1 <= bit0 || bb0 >= bit1) continue;   // no bit of this batch falls into the chunk
+                int nb = nb0, ex = ex0;
+                if (b > 0) {
+                    const int m = b * kPackThreads + tid;
+                    nb = (fin != ACT_SKIPALL && m < nmb) ? a.mb_nbits[first + m] : 0;
+                    int bt;
+                    ex = block_excl_scan<NW>(nb, wave_tot, &bt);
+                }
+                s_off[tid] = bb0 + ex;
+                s_end[tid] = bb0 + ex + nb;   // non-decreasing; the threads past the last MB hold bb1
+                __syncthreads();
+                // Word-parallel: thread t owns the words jw0 + t + q * kPackThreads of the batch's
+                // bits inside the chunk. It finds the MB that holds the word's first bit by a
+                // binary search over the end offsets and the next MB with bits when that one ends
+                // inside the word; the loads of both pieces of all its words are in flight
+                // together. MBs shorter than a word can put more pieces into one word: a loop.
+                const int jw0 = (int)(sk_max((long long)bb0, bit0) >> 5);
+                const int jw1 = (int)((sk_min((long long)bb1, bit1) - 1) >> 5);
+                const uint32_t* base = a.mb_bits + (size_t)(first + b * kPackThreads) * (kMbSlotBytes / 4);
+                uint32_t v[kPackWordsPerThread];
+                int more[kPackWordsPerThread];
+#pragma unroll
+                for (int q = 0; q < kPackWordsPerThread; q++) {
+                    const int jw = jw0 + tid + q * kPackThreads, wb = jw * 32, we = wb + 32;
+                    v[q] = 0u;
+                    more[q] = kPackThreads;
+                    if (jw > jw1) continue;
+                    const int m1 = pack_upper_bound(s_end, sk_max(wb, bb0));
+                    if (m1 >= kPackThreads || s_off[m1] >= we) continue;
+                    const int o1 = s_off[m1], e1 = s_end[m1];
+                    v[q] = pack_bits32(base + (size_t)m1 * (kMbSlotBytes / 4), e1 - o1, wb - o1);
+                    if (e1 >= we) continue;
+                    const int m2 = pack_upper_bound(s_end, e1);
+                    if (m2 >= kPackThreads || s_off[m2] >= we) continue;
+                    const int o2 = s_off[m2], e2 = s_end[m2];
+                    v[q] |= pack_bits32(base + (size_t)m2 * (kMbSlotBytes / 4), e2 - o2, wb - o2);
+                    if (e2 < we) more[q] = m2;
+                }
+#pragma unroll
+                for (int q = 0; q < kPackWordsPerThread; q++) {
+                    const int jw = jw0 + tid + q * kPackThreads, wb = jw * 32, we = wb + 32;
+                    if (jw > jw1) continue;
+                    int m = more[q];
+                    while (m < kPackThreads) {
+                        const int mm = pack_upper_bound(s_end, s_end[m]);
+                        if (mm >= kPackThreads || s_off[mm] >= we) break;
+                        v[q] |= pack_bits32(base + (size_t)mm * (kMbSlotBytes / 4), s_end[mm] - s_off[mm], wb - s_off[mm]);
+                        m = s_end[mm] < we ? mm : kPackThreads;
+                    }
+                    chunk[jw - cw0] |= v[q];
+                }
+                __syncthreads();   // s_off / s_end are rewritten by the next batch
             }
-            v = (lo >> sh) | (k >= 1 ? hi << (32 - sh) : 0u);
-        }
-        if (j == w0 || j == w1) {
-            if (v) atomicOr(&dst[j], v);
-        } else {
-            dst[j] = v;
-        }
-    }
-}
-
-__device__ __forceinline__ uint8_t rbsp_byte(uint32_t word, int q) { return ep_rbsp_byte(word, q); }
-
-// EP kernels: grid (tile, slice); a block loops over the slice's NALs (one for every
-// slice but the sub-sliced I ones, so P pictures launch no per-NAL blocks).
-// Per-thread EP decisions for 16 bytes starting at i0; `carry()` = last non-zero
-// byte index before the tile, asked for after the workgroup barrier (k_ep_count
-// hands it over through LDS). Returns the insertion count; bytes and insertion
-// mask through the out parameters.
-template <class Carry>
-__device__ __forceinline__ int ep_thread(const uint32_t* rbsp, int n, int t0, Carry carry, int* scan_lds,
-                                         uint8_t* by, uint32_t* insmask) {
-    const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
-    const int i0 = t0 + tid * 16;
-    int lastnz = -1;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int iq = i0 + 4 * q;
-        const uint32_t wd = iq < n ? rbsp[iq >> 2] : 0u;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            by[4 * q + j] = rbsp_byte(wd, j);
-            if (iq + j < n && by[4 * q + j]) lastnz = iq + j;
-        }
-    }
-    const int incl = wave_incl_scan_max(lastnz);
-    int ex = __shfl_up(incl, 1);
-    if (ln == 0) ex = -1;
-    if (ln == 63) scan_lds[wv] = incl;
-    __syncthreads();
-    int prev = carry();
-    for (int k = 0; k < wv; k++) prev = max(prev, scan_lds[k]);
-    prev = max(prev, ex);
-    int ins = 0;
-    uint32_t mask = 0;
-#pragma unroll
-    for (int q = 0; q < 16; q++) {
-        const int i = i0 + q;
-        if (i < n) {
-            const int z = i - 1 - prev;
-            if (by[q] <= 3 && z >= 2 && !(z & 1)) {
-                ins++;
-                mask |= 1u << q;
+            __syncthreads();
+            if (tid < 2) {   // trailing bits: at most 30, two words
+                const int tp = hb + total, jw = (tp >> 5) + tid;
+                if (jw <= ((tp + tb - 1) >> 5) && jw >= cw0 && jw < cw0 + kPackWords)
+                    chunk[jw - cw0] |= pack_bits32(tail, tb, jw * 32 - tp);
             }
-            if (by[q]) prev = i;
-        }
-    }
-    *insmask = mask;
-    return ins;
-}
-
-// The carry of every tile (h264_ep.h) is taken here and stored, not in k_ep_write:
-// k_ep_write clears the RBSP words of its own tile, so a tile that looked backwards
-// there could read words its predecessor tile has already zeroed. Here every
-// workgroup only reads bytes that the kernels before this one finished; k_ep_write
-// loads the stored carry.
-__global__ __launch_bounds__(256) void k_ep_count(FrameArgs a) {
-    __shared__ int scan_lds[4];
-    __shared__ int red[4];
-    __shared__ int sh_carry;
-    const int s = blockIdx.y, t = blockIdx.x;
-    // K10: the slice sizes are final since k_slice_scan and nothing else in this kernel
-    // touches *a.rc; before the NAL loop, so that an uncoded slice 0 does not skip it
-    if (s == 0 && t == 0 && threadIdx.x < 64)
-        rc_account_wave(a, a.slice_info, a.num_slices * a.nal_per_slice, 4, a.nal_per_slice);
-    const int nn = slice_nals(a, a.tasks[s]);
-    for (int j = 0; j < nn; j++) {
-        const int nal = s * a.nal_per_slice + j;
-        const int n = a.slice_info[4 * nal];
-        const int t0 = t * kTile;
-        if (t0 >= n) continue;
-        const uint32_t* rbsp = nal_rbsp(a, s, j);
-        if (threadIdx.x < 64) {
-            const int c = ep_tile_carry(rbsp, t0, lane_id(), 64, [](bool p) { return (uint64_t)__ballot(p); });
-            if (threadIdx.x == 0) {
-                sh_carry = c;
-                a.tile_carry[nal * a.max_tiles + t] = c;
+            __syncthreads();
+            // emulation prevention of the chunk into sOut
+            const int i0 = cb + tid * kEpLaneBytes;
+            const int cnt = sk_clip(n - i0, 0, kEpLaneBytes);
+            uint8_t by[kEpLaneBytes];
+#pragma unroll
+            for (int q = 0; q < kEpLaneBytes / 4; q++) {
+                const uint32_t wd = 4 * q < cnt ? chunk[tid * (kEpLaneBytes / 4) + q] : 0u;
+#pragma unroll
+                for (int r = 0; r < 4; r++) by[4 * q + r] = ep_rbsp_byte(wd, r);
             }
-        }
-        uint8_t by[16];
-        uint32_t mask;
-        int ins = ep_thread(rbsp, n, t0, [&] { return sh_carry; }, scan_lds, by, &mask);
-        for (int o = 32; o > 0; o >>= 1) ins += __shfl_down(ins, o);
-        if (lane_id() == 0) red[threadIdx.x >> 6] = ins;
-        __syncthreads();
-        if (threadIdx.x == 0) a.tile_ins[nal * a.max_tiles + t] = red[0] + red[1] + red[2] + red[3];
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ep_write(FrameArgs a) {
-    __shared__ int scan_lds[4];
-    __shared__ int wave_tot[5];
-    __shared__ int sh_before, sh_base;
-    __shared__ uint8_t sOut[kTile + kTile / 2 + 16];
-    const int s = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-    const SliceTask& task = a.tasks[s];
-    const int nn = slice_nals(a, task);
-    for (int j = 0; j < nn; j++) {
-    const int nal = s * a.nal_per_slice + j;
-    const int n = a.slice_info[4 * nal];
-    const int t0 = t * kTile;
-    if (t0 >= n) continue;
-    if (tid < 64) {
-        int b = 0;
-        for (int k = tid; k < t; k += 64) b += a.tile_ins[nal * a.max_tiles + k];
-        b = wave_sum(b);
-        // K5: the slot bytes of the NALs before this one (prefix + RBSP + insertions)
-        int base = 0;
-        for (int jj = 0; jj < j; jj++) {
-            const int q = s * a.nal_per_slice + jj, nq = a.slice_info[4 * q];
-            int ins_q = 0;
-            for (int k = tid; k * kTile < nq; k += 64) ins_q += a.tile_ins[q * a.max_tiles + k];
-            base += a.slice_info[4 * q + 1] + nq + wave_sum(ins_q);
-        }
-        if (tid == 0) {
-            sh_before = b;
-            sh_base = base;
-        }
-    }
-    uint32_t* rbsp = nal_rbsp(a, s, j);
-    uint8_t by[16];
-    uint32_t mask;
-    const int carry = a.tile_carry[nal * a.max_tiles + t];   // from k_ep_count: this kernel clears RBSP words
-    const int ins = ep_thread(rbsp, n, t0, [&] { return carry; }, scan_lds, by, &mask);
-    int tile_ins;
-    const int ex = block_excl_scan<4>(ins, wave_tot, &tile_ins);
-    const int i0 = t0 + tid * 16;
-    int o = tid * 16 + ex;
+            int own;
+            const uint32_t mask = ep_lane(
+                by, i0, cnt, carry,
+                [&](int v) {   // maximum over the lanes before this one
+                    const int incl = wave_incl_scan_max(v);
+                    int ex = __shfl_up(incl, 1);
+                    if (lane_id() == 0) ex = -1;
+                    if (lane_id() == 63) scan_lds[tid >> 6] = incl;
+                    __syncthreads();
+                    for (int k = 0; k < (tid >> 6); k++) ex = max(ex, scan_lds[k]);
+                    return ex;
+                },
+                &own);
+            for (int k = 0; k < NW; k++) carry = max(carry, scan_lds[k]);
+            int chunk_ins;
+            const int ex = block_excl_scan<NW>(__popc(mask), wave_tot, &chunk_ins);
+            int o = tid * kEpLaneBytes + ex;
 #pragma unroll
-    for (int q = 0; q < 16; q++) {
-        if (i0 + q < n) {
-            if (mask & (1u << q)) sOut[o++] = 3;
-            sOut[o++] = by[q];
+            for (int q = 0; q < kEpLaneBytes; q++) {
+                if (q < cnt) {
+                    if (mask & (1u << q)) sOut[o++] = 3;
+                    sOut[o++] = by[q];
+                }
+            }
+            __syncthreads();
+            // stream the stage to the slot: bytes up to a 16-byte boundary, vectors, bytes
+            const int len = clen + chunk_ins;
+            const int g0 = out_pos;
+            const int head = sk_min(len, (16 - (g0 & 15)) & 15);
+            if (tid < head) dst[g0 + tid] = sOut[tid];
+            const int nvec = (len - head) >> 4;
+            for (int v = tid; v < nvec; v += kPackThreads) {
+                const uint8_t* q = sOut + head + 16 * v;
+                uint4 x;
+                x.x = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
+                x.y = q[4] | (q[5] << 8) | (q[6] << 16) | ((uint32_t)q[7] << 24);
+                x.z = q[8] | (q[9] << 8) | (q[10] << 16) | ((uint32_t)q[11] << 24);
+                x.w = q[12] | (q[13] << 8) | (q[14] << 16) | ((uint32_t)q[15] << 24);
+                *reinterpret_cast<uint4*>(dst + g0 + head + 16 * v) = x;
+            }
+            const int tail0 = head + 16 * nvec;
+            if (tid < len - tail0) dst[g0 + tail0 + tid] = sOut[tail0 + tid];
+            out_pos += len;
+            __syncthreads();   // chunk / sOut / scan_lds are rewritten by the next pass
         }
+        slot_pos = out_pos;
     }
-    // self-clean the RBSP words of this tile for the next frame
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (i0 + 4 * q < n) rbsp[(i0 >> 2) + q] = 0u;
-    __syncthreads();
-    const int len = sk_min(n - t0, kTile) + tile_ins;
-    const int g0 = sh_base + a.slice_info[4 * nal + 1] + t0 + sh_before;
-    uint8_t* dst = a.host_out + (size_t)s * a.out_slot_bytes;
-    if (j > 0 && t == 0 && tid == 0) {   // this NAL's start code and header
-        const bool idr = task.final_action == ACT_I && task.idr_on_intra;
-        dst[sh_base] = 0; dst[sh_base + 1] = 0; dst[sh_base + 2] = 0; dst[sh_base + 3] = 1;
-        dst[sh_base + 4] = idr ? 0x65 : 0x41;
-    }
-    const int head = sk_min(len, (16 - (g0 & 15)) & 15);
-    if (tid < head) dst[g0 + tid] = sOut[tid];
-    const int nvec = (len - head) >> 4;
-    for (int v = tid; v < nvec; v += 256) {
-        const uint8_t* q = sOut + head + 16 * v;
-        uint4 x;
-        x.x = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
-        x.y = q[4] | (q[5] << 8) | (q[6] << 16) | ((uint32_t)q[7] << 24);
-        x.z = q[8] | (q[9] << 8) | (q[10] << 16) | ((uint32_t)q[11] << 24);
-        x.w = q[12] | (q[13] << 8) | (q[14] << 16) | ((uint32_t)q[15] << 24);
-        *reinterpret_cast<uint4*>(dst + g0 + head + 16 * v) = x;
-    }
-    const int tail0 = head + 16 * nvec;
-    if (tid < len - tail0) dst[g0 + tail0 + tid] = sOut[tail0 + tid];
-    if (j == nn - 1 && t0 + kTile >= n && tid == 0) a.host_size[s] = g0 + len;
-    __syncthreads();   // sOut / sh_* are rewritten by the next NAL
-    }
+    if (!kSizeOnly && tid == 0) a.host_size[s] = slot_pos;
 }
 
 // ---------------------------------------------------------------------------
 // Reference update: rec -> ref for coded slices, MV field for the next frame's
 // candidates. One workgroup per MB row segment of 16 MBs, 16-byte accesses.
-__global__ __launch_bounds__(256) void k_commit(FrameArgs a) {
+__global__ __launch_bounds__(256) void k_commit(FrameArgs a, int account) {
     const int mby = blockIdx.y, mbx0 = blockIdx.x * 16;
+    // K10 accounting of the H.264 chain: every NAL's size is final since k_slice_pack, this
+    // kernel runs behind it for every frame and ahead of the next frame's k_rc_qp, and
+    // nothing else in it touches *a.rc. Before the exits, so an uncoded slice 0 keeps it.
+    if (account && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64)
+        rc_account_wave(a, a.slice_info, a.num_slices * a.nal_per_slice, 4, a.nal_per_slice);
     const int s = mby / a.rows_per_slice;
     const int fin = a.tasks[s].final_action;
     if (fin == ACT_NONE) return;
@@ -3528,19 +3515,21 @@ void launch_rc_account(const FrameArgs& a, const int* sizes, int n, int stride, 
     hipLaunchKernelGGL(k_rc_account, dim3(1), dim3(64), 0, s, a, sizes, n, stride, per_slice);
 }
 
-// Transform / quantisation / reconstruction / CAVLC / slice scan of every coded slice.
+// Transform / quantisation / reconstruction / CAVLC of every coded slice.
 static void launch_code(const FrameArgs& a, hipStream_t s) {
     int nmb = a.mb_w * a.mb_h;
     hipLaunchKernelGGL(k_code_inter, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_intra_prep, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
-    if (a.rows_per_slice <= 4)
+    // Every I slice of a geometry is coded by the same kernel (split_i depends on the
+    // geometry alone): the sub-slice kernel where slices are split (K5, one wave per
+    // sub-slice), the wavefront kernel elsewhere. The other one would only exit.
+    if (a.nal_per_slice > 1)
+        hipLaunchKernelGGL(k_code_intra_sub, dim3((a.num_slices * a.nal_per_slice + 3) / 4), dim3(256), 0, s, a);
+    else if (a.rows_per_slice <= 4)
         hipLaunchKernelGGL(k_code_intra<4>, dim3(a.num_slices), dim3(64 * 5), 0, s, a);
     else
         hipLaunchKernelGGL(k_code_intra<kMaxRows - 1>, dim3(a.num_slices), dim3(64 * kMaxRows), 0, s, a);
-    if (a.nal_per_slice > 1)   // K5 sub-sliced I slices: one wave per sub-slice
-        hipLaunchKernelGGL(k_code_intra_sub, dim3((a.num_slices * a.nal_per_slice + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_cavlc, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_slice_scan, dim3(a.num_slices * a.nal_per_slice), dim3(256), 0, s, a);
 }
 
 void launch_encode(const FrameArgs& a, hipStream_t s, bool guard) {
@@ -3549,20 +3538,19 @@ void launch_encode(const FrameArgs& a, hipStream_t s, bool guard) {
     if (a.aq_strength > 0) hipLaunchKernelGGL(k_aq, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
     launch_code(a, s);
     if (guard && a.rc_redo) {   // K10 CBR: VBV overflow -> one coarser pass (kernels exit early otherwise)
+        // the guard needs the first pass's NAL sizes and nothing else of its bitstream
+        hipLaunchKernelGGL(k_slice_pack<true>, dim3(a.num_slices), dim3(kPackThreads), 0, s, a);
         hipLaunchKernelGGL(k_rc_guard, dim3(1), dim3(256), 0, s, a);
         FrameArgs b = a;
         b.gate = a.rc_redo;
         launch_code(b, s);
     }
-    hipLaunchKernelGGL(k_mb_concat, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
-    const dim3 tiles(a.max_tiles, a.num_slices);
-    hipLaunchKernelGGL(k_ep_count, tiles, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_ep_write, tiles, dim3(256), 0, s, a);   // K10 accounting: inside k_ep_count
+    hipLaunchKernelGGL(k_slice_pack<false>, dim3(a.num_slices), dim3(kPackThreads), 0, s, a);   // K10 accounting: k_commit
 }
 
-void launch_commit(const FrameArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_commit, dim3((a.mb_w + 15) / 16, a.mb_h), dim3(256), 0, s, a);
-    if (a.deblock) {
+void launch_commit(const FrameArgs& a, hipStream_t s, bool filter, bool account) {
+    hipLaunchKernelGGL(k_commit, dim3((a.mb_w + 15) / 16, a.mb_h), dim3(256), 0, s, a, account ? 1 : 0);
+    if (a.deblock && filter) {
         const int nmb = a.mb_w * a.mb_h;
         hipLaunchKernelGGL(k_deblock_prep, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_deblock_edges, dim3((nmb + 255) / 256), dim3(256), 0, s, a);

@@ -3,8 +3,9 @@
 // (csrc/kernels/h264_kernels.hip). Frame flow:
 //   H2D(BGRx) -> (overlay placement, only when it changed) -> [K1/K3 convert+damage,
 //   k_plan (stripe controller on the GPU), K4 ME, decide, K6 inter, K5/K6 intra, K8 CAVLC,
-//   K9 slice assembly into host-mapped packet slots, commit] (one hipGraph per src/prev
-//   parity) -> one sync -> packets. No host decision sits inside a frame.
+//   K9 slice assembly into host-mapped packet slots] (one hipGraph per src/prev parity)
+//   -> one sync -> packets; behind it, not waited on: commit + K10 accounting (+ K7
+//   deblocking when a slice of the frame can be filtered), a second graph. No host decision sits inside a frame.
 #include "encoder_iface.h"
 #include "trace.h"
 #include "../kernels/h264_gpu.h"
@@ -62,6 +63,8 @@ class HipBackend : public EncoderBackend {
         for (auto& gx : graph_exec_)
             if (gx) hipGraphExecDestroy(gx);
         for (auto& gx : post_exec_)
+            if (gx) hipGraphExecDestroy(gx);
+        for (auto& gx : post_short_exec_)
             if (gx) hipGraphExecDestroy(gx);
         for (void* p : dev_allocs_) hipFree(p);
         for (void* p : host_allocs_) hipHostFree(p);
@@ -303,7 +306,10 @@ class HipBackend : public EncoderBackend {
         // after part 0 on ROCm 7: packets read back empty. Two launches it is.)
         run_graph(graph_exec_[p], 0);
         HIPCHECK(hipEventRecord(ev_[3 * p + 2], stream_));
-        run_graph(post_exec_[p], 1);
+        // Part 1 without the deblocking kernels when no slice of this frame can be filtered.
+        // H.264 only: HEVC and AV1 filter in their own back ends and replay part 1 as before.
+        if (cfg_.codec != 0 || can_filter(h_key_snap_[p])) run_graph(post_exec_[p], 1);
+        else run_graph(post_short_exec_[p], 2);
         staged_ = false;
         launched_++;
         parity_ = launched_ & 1;
@@ -446,6 +452,8 @@ class HipBackend : public EncoderBackend {
             RcState rc;
             memcpy(&rc, head.data() + sizeof(StateHeader) + sizeof(StripeState) * (ns + 1), sizeof(rc));
             rc.seq = __atomic_load_n(&h_key_seq_[5], __ATOMIC_SEQ_CST);
+            dev_rc_mode_ = rc.mode;   // can_filter(): the device controller now runs in the imported mode
+            dev_rc_seq_ = rc.seq;
             HIPCHECK(hipMemcpyAsync(args_.rc, &rc, sizeof(rc), hipMemcpyHostToDevice, stream_));
             HIPCHECK(hipStreamSynchronize(stream_));
         }
@@ -695,6 +703,7 @@ class HipBackend : public EncoderBackend {
             a.gate = nullptr;
             a.rc_fps = cfg_.fps;
             h_key_seq_[3] = cfg_.rc_mode;
+            dev_rc_mode_ = cfg_.rc_mode;
             h_key_seq_[4] = cfg_.bitrate_kbps;
         }
         a.db = dmalloc<DbInfo>(nmb);
@@ -707,17 +716,18 @@ class HipBackend : public EncoderBackend {
         // K5: split I slices put one NAL per sub-slice (h264_encoder.h intra_split)
         const bool can_split = cfg_.codec == 0 && g_.mb_w > kIntraSubMbs;
         a.nal_per_slice = can_split ? max_nals_per_slice(g_.rows_per_slice, g_.mb_w) : 1;
-        a.sub_rbsp_words = (kIntraSubMbs * gpu::kMbSlotBytes + 1024) / 4;
-        a.rbsp_slot_words = std::max((max_slice_mbs * gpu::kMbSlotBytes + 1024) / 4,
-                                     can_split ? a.nal_per_slice * a.sub_rbsp_words : 0);
-        a.rbsp = dmalloc<uint32_t>((size_t)ns * a.rbsp_slot_words);
-        a.mb_off = dmalloc<int>(nmb);
+        if (cfg_.codec == 0 && max_slice_mbs > gpu::kPackMaxSliceMbs)
+            throw std::runtime_error("H.264: more than " + std::to_string(gpu::kPackMaxSliceMbs) +
+                                     " macroblocks per slice is not supported");   // k_slice_pack's bbase[]
         a.slice_info = dmalloc<int>(4 * (size_t)ns * a.nal_per_slice);
-        a.max_tiles = (a.rbsp_slot_words * 4 + 4095) / 4096;
-        a.tile_carry = dmalloc<int>((size_t)ns * a.nal_per_slice * a.max_tiles);
-        a.tile_ins = dmalloc<int>((size_t)ns * a.nal_per_slice * a.max_tiles);
+        // A slice's RBSP at its worst: every MB fills its CAVLC slot, plus the slice header
+        // (per sub-slice NAL where I slices are split). The RBSP itself only exists in LDS
+        // (k_slice_pack); the bound sizes the host slot.
+        const size_t sub_rbsp = (size_t)kIntraSubMbs * gpu::kMbSlotBytes + 1024;
+        const size_t max_rbsp = std::max((size_t)max_slice_mbs * gpu::kMbSlotBytes + 1024,
+                                         can_split ? a.nal_per_slice * sub_rbsp : (size_t)0);
         // worst case: header + SPS/PPS + 3/2 emulation-prevention growth, 64-byte multiple
-        size_t slot = ((size_t)a.rbsp_slot_words * 4 * 3 / 2 + 1024 + 63) & ~(size_t)63;
+        size_t slot = (max_rbsp * 3 / 2 + 1024 + 63) & ~(size_t)63;
         a.out_slot_bytes = (int)slot;
         void* dptr = nullptr;
         for (int p = 0; p < 2; p++) {   // host outputs per parity (two frames in flight)
@@ -790,13 +800,16 @@ class HipBackend : public EncoderBackend {
 
     void invalidate_graphs() {
         ov_resend_ = true;
-        for (auto* set : {graph_exec_, post_exec_})
+        for (auto* set : {graph_exec_, post_exec_, post_short_exec_})
             for (int i = 0; i < 2; i++)
                 if (set[i]) { hipGraphExecDestroy(set[i]); set[i] = nullptr; }
     }
 
-    // part 0: convert/damage -> ... -> packets; part 1: commit (+ deblocking).
-    // rbsp is self-cleaning (k_ep_write); stripe flags are cleared by k_plan. The overlay
+    // part 0: convert/damage -> ... -> packets; part 1: commit (+ deblocking); part 2: commit
+    // alone, for frames in which no slice can be filtered (can_filter).
+    // The H.264 chain's K10 accounting runs in k_commit (both commit graphs), behind
+    // k_slice_pack; every host reader of the controller state (rc_stats, export_state)
+    // synchronises the stream, so behind part 1. Stripe flags are cleared by k_plan. The overlay
     // placement is not part of the graph: launch() copies it ahead of the graph when it changed.
     void enqueue(int part) {
         if (part == 0) {
@@ -823,8 +836,26 @@ class HipBackend : public EncoderBackend {
                 gpu::launch_encode(args_, stream_, graph_guard_);
             }
         } else {
-            gpu::launch_commit(args_, stream_);
+            gpu::launch_commit(args_, stream_, part == 1, cfg_.codec == 0);
         }
+    }
+
+    // Whether a slice of the frame launched with key snapshot `snap` (h_key_snap_) can be
+    // deblocked, i.e. whether part 1 needs its deblocking kernels. Off: never. On: always.
+    // Automatic (slices at QP >= kAutoDeblockQp): not when max_slice_qp, for the frame's
+    // rate mode and QPs, stays below the threshold - every CQP / CRF session at the default
+    // QPs. CBR reaches every QP and always takes the long graph. The rate mode is the device
+    // controller's at that frame: k_rc_qp takes the snapshot's mode when its set_rate()
+    // counter moved (as here), else keeps its own (initial, or imported with a state).
+    bool can_filter(const int* snap) {
+        if (!args_.deblock) return false;
+        if (snap[5] != dev_rc_seq_) {
+            dev_rc_seq_ = snap[5];
+            dev_rc_mode_ = snap[3];
+        }
+        if (args_.deblock != 2) return true;
+        const int qp = snap[1] > 0 ? snap[1] : cfg_.qp, pqp = snap[2] > 0 ? snap[2] : cfg_.paint_qp;
+        return max_slice_qp(dev_rc_mode_, qp, pqp) >= kAutoDeblockQp;
     }
 
     void run_graph(hipGraphExec_t& gx, int part) {
@@ -1152,6 +1183,8 @@ class HipBackend : public EncoderBackend {
     OverlayParams ov_pending_[kOverlaySlots];
     uint8_t* ov_stage_ = nullptr;
     hipGraphExec_t post_exec_[2] = {nullptr, nullptr};
+    hipGraphExec_t post_short_exec_[2] = {nullptr, nullptr};   // part 1 without the deblocking kernels
+    int dev_rc_mode_ = 0, dev_rc_seq_ = 0;   // rate mode of the device controller and the set_rate() counter it has seen
     bool use_graphs_ = getenv("SK_NO_GRAPHS") == nullptr;
     // Blocking copies are ordered on the encoder's own stream: a copy on the legacy
     // stream fails while any stream of the process is capturing a graph (several
