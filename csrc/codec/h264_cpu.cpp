@@ -973,5 +973,50 @@ void CpuH264Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id,
     finish_frame();
 }
 
+// ---- session state (h264_state.h) --------------------------------------------
+// Where a section lives in this encoder. The header and the controller's stripe states have
+// no storage of the blob's shape: nullptr.
+static void* state_section_ptr(CpuH264Encoder& e, const StateSection& s) {
+    switch (s.kind) {
+        case ST_RC: return &e.ctl_.rc();
+        case ST_REF: return e.ref[s.plane].data();
+        case ST_REF1: return e.ref1[s.plane].data();
+        case ST_SRC: return e.prev[s.plane].data();   // after finish_frame the source lives in prev
+        case ST_MVFIELD: return e.mvfield.data();
+        case ST_LTR_STATE: return e.ltr_state.data();
+        case ST_LTR_SLOT: return e.ltr_planes[s.slot][s.plane].data();
+        default: return nullptr;
+    }
+}
+
+void cpu_export_state(CpuH264Encoder& e, void* dst) {
+    state_sections(e.g, e.ltr_slots_, [&](const StateSection& s) {
+        uint8_t* o = static_cast<uint8_t*>(dst) + s.off;
+        if (s.kind == ST_HEADER) {
+            StateHeader h;
+            state_header(e.cfg, e.g, e.first_frame ? 0 : 1, e.ctl_.qp(), e.ctl_.paint_qp(), h);
+            memcpy(o, &h, sizeof(h));
+        } else if (s.kind == ST_STRIPES) {
+            e.ctl_.export_states(reinterpret_cast<StripeState*>(o));
+        } else {
+            memcpy(o, state_section_ptr(e, s), s.bytes);
+        }
+    });
+}
+
+bool cpu_import_state(CpuH264Encoder& e, const void* src) {
+    StateHeader h;
+    memcpy(&h, src, sizeof(h));
+    if (!state_header_matches(e.cfg, e.g, h)) return false;
+    state_sections(e.g, e.ltr_slots_, [&](const StateSection& s) {
+        const uint8_t* i = static_cast<const uint8_t*>(src) + s.off;
+        if (s.kind == ST_STRIPES) e.ctl_.import_states(reinterpret_cast<const StripeState*>(i));
+        else if (s.kind != ST_HEADER) memcpy(state_section_ptr(e, s), i, s.bytes);
+    });
+    e.first_frame = !h.started;
+    e.set_qp(h.qp, h.paint_qp);
+    return true;
+}
+
 }  // namespace h264
 }  // namespace sk

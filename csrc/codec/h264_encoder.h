@@ -417,69 +417,6 @@ class Controller {
 };
 
 
-
-// ---- session state transfer --------------------------------------------------
-// Portable snapshot of everything that carries over from one frame to the next,
-// identical for the CPU and HIP backends (so a session can move between GPUs, or
-// between a GPU and the CPU reference, without an IDR):
-//   StateHeader | StripeState[num_slices + 1] (committed; last = picture state) |
-//   ref Y U V | ref1 Y U V (second reference) | last source Y U V (damage baseline) |
-//   mvfield int16[2 * num_mbs]
-// Session state (parallel/migrate.py), the same for every codec and both backends:
-//   StateHeader | StripeState[num_slices + 1] (controller; the last is the picture's, whose
-//   frame_num is also the next HEVC POC) | RcState (K10) | ref | ref1 | last source
-//   (4:2:0 planes) | MV field. The reference planes are what the next frame predicts from
-//   (HEVC: after deblocking + SAO, AV1: after loop filter + CDEF).
-// With the H.264 long-term cache on (ltr_slots > 0) the blob is version 4: the version-3 layout, then
-//   LtrState[num_slices + 1] | slot 0 Y U V | slot 1 Y U V | ...  Without it the blob stays version 3.
-struct StateHeader {
-    char magic[4];          // "SKH4"
-    int32_t version;        // 3 (codec, RcState); 4 = 3 + long-term cache (EncoderConfig::ltr_slots > 0)
-    int32_t W, H, stripe_height, fullframe, num_slices;
-    int32_t started;        // a frame has been encoded (else the next one is all-dirty)
-    int32_t qp, paint_qp;   // rate-control QPs in force
-    int32_t codec;          // EncoderConfig::codec
-    int32_t ltr_slots;      // version 4: slot plane sets that follow (0 in version 3, where the word was reserved)
-    int32_t reserved[4];
-};
-static_assert(sizeof(StateHeader) == 64, "StateHeader layout");
-
-inline size_t state_plane_bytes(const Geometry& g) {
-    return (size_t)g.stride_y * g.plane_h_y + 2 * (size_t)g.stride_c * g.plane_h_c;
-}
-inline size_t state_head_bytes(const Geometry& g) {   // header + controller + rate control
-    return sizeof(StateHeader) + sizeof(StripeState) * (size_t)(g.num_slices + 1) + sizeof(RcState);
-}
-// Version 4 appends LtrState[num_slices + 1] (last = the picture's, full-frame mode) and the slot plane sets.
-inline size_t state_ltr_bytes(const Geometry& g, int ltr_slots) {
-    return ltr_slots > 0 ? sizeof(ltr::LtrState) * (size_t)(g.num_slices + 1) + (size_t)ltr_slots * state_plane_bytes(g) : 0;
-}
-inline size_t state_bytes(const Geometry& g, int ltr_slots = 0) {
-    return state_head_bytes(g) + 3 * state_plane_bytes(g) + sizeof(int16_t) * 2 * (size_t)g.num_mbs() +
-           state_ltr_bytes(g, ltr_slots);
-}
-inline void state_header(const EncoderConfig& c, const Geometry& g, int started, int qp, int paint_qp,
-                         StateHeader& h) {
-    memset(&h, 0, sizeof(h));
-    memcpy(h.magic, "SKH4", 4);
-    h.version = ltr_slots_of(c) > 0 ? 4 : 3;
-    h.ltr_slots = ltr_slots_of(c);
-    h.codec = c.codec;
-    h.W = g.W;
-    h.H = g.H;
-    h.stripe_height = c.stripe_height;
-    h.fullframe = c.fullframe;
-    h.num_slices = g.num_slices;
-    h.started = started;
-    h.qp = qp;
-    h.paint_qp = paint_qp;
-}
-inline bool state_header_matches(const EncoderConfig& c, const Geometry& g, const StateHeader& h) {
-    return memcmp(h.magic, "SKH4", 4) == 0 && h.version == (ltr_slots_of(c) > 0 ? 4 : 3) &&
-           h.ltr_slots == ltr_slots_of(c) && h.codec == c.codec && h.W == g.W && h.H == g.H &&
-           h.stripe_height == c.stripe_height && h.fullframe == c.fullframe && h.num_slices == g.num_slices;
-}
-
 // ---- bitstream packaging (host) -------------------------------------------
 int choose_level_idc(int mb_w, int mb_h, float fps, int dpb_frames = 0);
 // SPS + PPS NAL units (Annex-B, with start codes) for a picture of w x h pixels.
@@ -493,3 +430,5 @@ void write_stripe_header(uint8_t* p, int key, uint16_t frame_id, int y, int w, i
 
 }  // namespace h264
 }  // namespace sk
+
+#include "h264_state.h"   // session state transfer: the blob's layout

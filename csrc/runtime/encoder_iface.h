@@ -58,7 +58,7 @@ class EncoderBackend {
         set_last_error("this encoder takes BGRx input only");
         return -1;
     }
-    // Session state transfer (h264::StateHeader layout). `on_device`: the buffer is
+    // Session state transfer (codec/h264_state.h layout). `on_device`: the buffer is
     // device memory of this encoder's GPU (HIP backend) instead of host memory.
     virtual int64_t state_bytes() { return -1; }
     virtual int export_state(void* dst, int on_device) { (void)dst; (void)on_device; return -1; }

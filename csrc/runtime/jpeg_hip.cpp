@@ -7,21 +7,11 @@
 //      segment read straight out of host-mapped memory.
 #include "encoder_iface.h"
 #include "trace.h"
+#include "hip_util.h"
 #include "../kernels/jpeg_gpu.h"
-#include <hip/hip_runtime.h>
-#include <stdexcept>
-#include <string.h>
-#include <string>
 
 namespace sk {
 namespace {
-
-#define HIPCHECK(x)                                                                     \
-    do {                                                                                \
-        hipError_t e__ = (x);                                                           \
-        if (e__ != hipSuccess)                                                          \
-            throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e__)); \
-    } while (0)
 
 using namespace jpeg;
 
@@ -41,14 +31,14 @@ class HipJpegBackend : public EncoderBackend {
         HIPCHECK(hipSetDevice(device_));
         warm_copy_engines(device_);
         HIPCHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        mem_.stream = stream_;
         alloc();
     }
     ~HipJpegBackend() override {
         hipSetDevice(device_);
         for (auto& g : graph_)
             if (g) hipGraphExecDestroy(g);
-        for (void* p : dev_) hipFree(p);
-        for (void* p : host_) hipHostFree(p);
+        mem_.free_all();
         for (auto* f : frame_)
             if (f) hipFree(f);
         hipStreamDestroy(stream_);
@@ -56,7 +46,7 @@ class HipJpegBackend : public EncoderBackend {
 
     void request_keyframe() override {
         // consumed by the next frame's stripe plan (host-mapped counter)
-        __atomic_add_fetch(h_key_seq_, 1, __ATOMIC_SEQ_CST);
+        __atomic_add_fetch(key_seq_.host, 1, __ATOMIC_SEQ_CST);
     }
 
     int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
@@ -93,9 +83,9 @@ class HipJpegBackend : public EncoderBackend {
         run_graph();
         HIPCHECK(hipStreamSynchronize(stream_));
         for (int s = 0; s < L_.num_stripes; s++) {
-            const int act = h_action_[s];
+            const int act = action_.host[s];
             if (act < 0) continue;
-            const int n = h_size_[s];
+            const int n = size_.host[s];
             if (n <= 0 || n > a_.out_slot) throw std::runtime_error("JPEG stripe size out of range");
             const std::vector<uint8_t>& hdr = hdr_[act][s == L_.num_stripes - 1 ? 1 : 0];
             h264::EncodedPacket pk;
@@ -108,7 +98,7 @@ class HipJpegBackend : public EncoderBackend {
                                     (uint8_t)pk.y};
             pk.data.insert(pk.data.end(), pre, pre + 4);
             pk.data.insert(pk.data.end(), hdr.begin(), hdr.end());
-            const uint8_t* seg = h_out_ + (size_t)s * a_.out_slot;
+            const uint8_t* seg = out_.host + (size_t)s * a_.out_slot;
             pk.data.insert(pk.data.end(), seg, seg + n);
             packets_.push_back(std::move(pk));
         }
@@ -135,23 +125,6 @@ class HipJpegBackend : public EncoderBackend {
     }
 
    private:
-    template <class T>
-    T* dmalloc(size_t count) {
-        void* p = nullptr;
-        HIPCHECK(hipMalloc(&p, count * sizeof(T)));
-        HIPCHECK(hipMemsetAsync(p, 0, count * sizeof(T), stream_));
-        dev_.push_back(p);
-        return (T*)p;
-    }
-    template <class T>
-    T* hmalloc(size_t count, unsigned flags) {
-        void* p = nullptr;
-        HIPCHECK(hipHostMalloc(&p, count * sizeof(T), flags));
-        memset(p, 0, count * sizeof(T));
-        host_.push_back(p);
-        return (T*)p;
-    }
-
     void alloc() {
         const int ns = L_.num_stripes;
         const int bps = (cfg_.stripe_height / 16) * L_.mcu_w * 6;
@@ -165,44 +138,37 @@ class HipJpegBackend : public EncoderBackend {
         a_.blocks_per_stripe = bps;
         a_.stride = -1;
         for (int i = 0; i < 2; i++) {
-            dirty_[i] = dmalloc<int>(ns);
-            state_[i] = dmalloc<JpegStripeState>(ns);
+            dirty_[i] = mem_.dmalloc<int>(ns);
+            state_[i] = mem_.dmalloc<JpegStripeState>(ns);
         }
-        a_.action = dmalloc<int>(ns);
-        a_.key_now = dmalloc<int>(1);
+        a_.action = mem_.dmalloc<int>(ns);
+        a_.key_now = mem_.dmalloc<int>(1);
         a_.use_paint_over = cfg_.use_paint_over;
         a_.paint_over_trigger = cfg_.paint_over_trigger;
-        JpegTables* dt = dmalloc<JpegTables>(2);
+        JpegTables* dt = mem_.dmalloc<JpegTables>(2);
         HIPCHECK(hipMemcpyAsync(dt, tab_, sizeof(tab_), hipMemcpyHostToDevice, stream_));
         HIPCHECK(hipStreamSynchronize(stream_));
         a_.tabs = dt;
-        a_.coef = dmalloc<int16_t>(nb * 64);
-        a_.dc = dmalloc<int16_t>(nb);
-        a_.dcdiff = dmalloc<int16_t>(nb);
-        a_.ac_bits = dmalloc<int>(nb);
-        a_.blk_off = dmalloc<int>(nb);
-        a_.stripe_bits = dmalloc<int>(ns);
+        a_.coef = mem_.dmalloc<int16_t>(nb * 64);
+        a_.dc = mem_.dmalloc<int16_t>(nb);
+        a_.dcdiff = mem_.dmalloc<int16_t>(nb);
+        a_.ac_bits = mem_.dmalloc<int>(nb);
+        a_.blk_off = mem_.dmalloc<int>(nb);
+        a_.stripe_bits = mem_.dmalloc<int>(ns);
         const size_t slot_bytes = ((size_t)bps * gpu::kMaxBlockBytes + 64 + 15) & ~(size_t)15;
         a_.bits_slot_words = (int)(slot_bytes / 4);
-        a_.bits = dmalloc<uint32_t>((size_t)ns * a_.bits_slot_words);
+        a_.bits = mem_.dmalloc<uint32_t>((size_t)ns * a_.bits_slot_words);
         a_.out_slot = (int)slot_bytes;
         a_.max_tiles = (int)(((size_t)bps * 208 + gpu::kTileBytes - 1) / gpu::kTileBytes);
-        a_.tile_ff = dmalloc<int>((size_t)ns * a_.max_tiles);
-        h_out_ = hmalloc<uint8_t>((size_t)ns * slot_bytes, hipHostMallocMapped);
-        h_size_ = hmalloc<int>(ns, hipHostMallocMapped);
-        h_action_ = hmalloc<int>(ns, hipHostMallocMapped);
-        h_key_seq_ = hmalloc<int>(1, hipHostMallocMapped);
-        a_.host_out = dev_ptr(h_out_);
-        a_.host_size = dev_ptr(h_size_);
-        a_.host_action = dev_ptr(h_action_);
-        a_.key_seq = dev_ptr(h_key_seq_);
-    }
-
-    template <class T>
-    T* dev_ptr(T* host) {
-        void* dp = nullptr;
-        HIPCHECK(hipHostGetDevicePointer(&dp, host, 0));
-        return (T*)dp;
+        a_.tile_ff = mem_.dmalloc<int>((size_t)ns * a_.max_tiles);
+        out_ = mem_.mapped<uint8_t>((size_t)ns * slot_bytes, hipHostMallocMapped);
+        size_ = mem_.mapped<int>(ns, hipHostMallocMapped);
+        action_ = mem_.mapped<int>(ns, hipHostMallocMapped);
+        key_seq_ = mem_.mapped<int>(1, hipHostMallocMapped);
+        a_.host_out = out_.dev;
+        a_.host_size = size_.dev;
+        a_.host_action = action_.dev;
+        a_.key_seq = key_seq_.dev;
     }
 
     void run_graph() {
@@ -230,13 +196,11 @@ class HipJpegBackend : public EncoderBackend {
     size_t frame_cap_ = 0;
     int parity_ = 0;
     bool first_ = true;
-    int* h_action_ = nullptr;
-    int* h_key_seq_ = nullptr;
     int* dirty_[2] = {nullptr, nullptr};
     JpegStripeState* state_[2] = {nullptr, nullptr};
-    int* h_size_ = nullptr;
-    uint8_t* h_out_ = nullptr;
-    std::vector<void*> dev_, host_;
+    Mapped<uint8_t> out_;                    // entropy segments, one slot per stripe
+    Mapped<int> size_, action_, key_seq_;    // per-stripe sizes and actions; request_keyframe() counter
+    HipAllocs mem_;
     hipGraphExec_t graph_[2] = {nullptr, nullptr};
 };
 

@@ -9,6 +9,8 @@
 #include <string>
 #include <mutex>
 #include <stdlib.h>
+#include <type_traits>
+#include <utility>
 
 namespace sk {
 
@@ -40,90 +42,77 @@ struct HostYuv {
     }
 };
 
-// Session state of a CPU encoder (h264_encoder.h StateHeader layout); HEVC / AV1 keep
-// all their inter-frame state in the shared front end (references, controller, K10).
-int cpu_export_state(h264::CpuH264Encoder& e, void* dst, int on_device) {
-    if (on_device) return -1;
-    uint8_t* o = static_cast<uint8_t*>(dst);
-    h264::StateHeader h;
-    h264::state_header(e.cfg, e.g, e.first_frame ? 0 : 1, e.ctl_.qp(), e.ctl_.paint_qp(), h);
-    memcpy(o, &h, sizeof(h));
-    o += sizeof(h);
-    e.ctl_.export_states(reinterpret_cast<h264::StripeState*>(o));
-    o += sizeof(h264::StripeState) * (e.g.num_slices + 1);
-    memcpy(o, &e.ctl_.rc(), sizeof(h264::RcState));
-    o += sizeof(h264::RcState);
-    for (auto* planes : {e.ref, e.ref1, e.prev})
-        for (int p = 0; p < 3; p++) {
-            memcpy(o, planes[p].data(), planes[p].size());
-            o += planes[p].size();
-        }
-    memcpy(o, e.mvfield.data(), e.mvfield.size() * sizeof(int16_t));
-    o += e.mvfield.size() * sizeof(int16_t);
-    if (e.ltr_slots_) {   // version 4: the long-term cache follows the version-3 layout
-        memcpy(o, e.ltr_state.data(), e.ltr_state.size() * sizeof(ltr::LtrState));
-        o += e.ltr_state.size() * sizeof(ltr::LtrState);
-        for (int j = 0; j < e.ltr_slots_; j++)
-            for (int p = 0; p < 3; p++) {
-                memcpy(o, e.ltr_planes[j][p].data(), e.ltr_planes[j][p].size());
-                o += e.ltr_planes[j][p].size();
-            }
-    }
-    return 0;
+// The shared front end of a CPU encoder (references, controller, K10, damage baseline): the
+// H.264 encoder itself, `fe` of the HEVC and AV1 encoders.
+h264::CpuH264Encoder& front(h264::CpuH264Encoder& e) { return e; }
+template <class Enc>
+h264::CpuH264Encoder& front(Enc& e) { return e.fe; }
+
+// debug_buffer view: data and byte count (-1: no such name)
+using DebugBuf = std::pair<const void*, int64_t>;
+template <class V>
+DebugBuf bytes_of(const V& v) { return {v.data(), (int64_t)(v.size() * sizeof(*v.data()))}; }
+
+// The debug_buffer names of each codec's own buffers; the front end's are resolved by CpuBackend.
+DebugBuf codec_debug(h264::CpuH264Encoder& e, const std::string& s) {
+    if (s == "ref1_y") return bytes_of(e.ref1[0]);
+    if (s == "ltr_state") return bytes_of(e.ltr_state);
+    if (s == "ltr_task") return bytes_of(e.ltr_task);
+    if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
+        s[3] < '0' + e.ltr_slots_) return bytes_of(e.ltr_planes[s[3] - '0'][0]);
+    if (s == "mbs") return bytes_of(e.mbs);
+    if (s == "coefs") return bytes_of(e.coefs);
+    if (s == "mb_dirty") return bytes_of(e.mb_dirty);
+    if (s == "aq") return bytes_of(e.aq);
+    if (s == "fs_mv") return bytes_of(e.fs_mv);
+    return {nullptr, -1};
+}
+DebugBuf codec_debug(hevc::CpuHevcEncoder& e, const std::string& s) {
+    if (s == "cus") return bytes_of(e.cus);
+    if (s == "sao") return bytes_of(e.sao);
+    if (s == "coefs") return bytes_of(e.coefs);
+    if (s == "bin_n") return bytes_of(e.bin_n);
+    if (s == "pc_dbg") return bytes_of(e.pc_dbg_);
+    return {nullptr, -1};
+}
+DebugBuf codec_debug(av1::CpuAv1Encoder& e, const std::string& s) {
+    if (s == "blk") return bytes_of(e.blk);
+    if (s == "levels") return bytes_of(e.lev);
+    if (s == "av1_geo") return {&e.geo, (int64_t)sizeof(av1::Av1Geo)};
+    if (s == "av1_qidx") return {&e.fp.qidx, 4};
+    return {nullptr, -1};
 }
 
-int cpu_import_state(h264::CpuH264Encoder& e, const void* src, int on_device) {
-    if (on_device) return -1;
-    const uint8_t* i = static_cast<const uint8_t*>(src);
-    h264::StateHeader h;
-    memcpy(&h, i, sizeof(h));
-    if (!h264::state_header_matches(e.cfg, e.g, h)) {
-        set_last_error("encoder state does not match this encoder's geometry / codec");
-        return -1;
-    }
-    i += sizeof(h);
-    e.ctl_.import_states(reinterpret_cast<const h264::StripeState*>(i));
-    i += sizeof(h264::StripeState) * (e.g.num_slices + 1);
-    memcpy(&e.ctl_.rc(), i, sizeof(h264::RcState));
-    i += sizeof(h264::RcState);
-    for (auto* planes : {e.ref, e.ref1, e.prev})
-        for (int p = 0; p < 3; p++) {
-            memcpy(planes[p].data(), i, planes[p].size());
-            i += planes[p].size();
-        }
-    memcpy(e.mvfield.data(), i, e.mvfield.size() * sizeof(int16_t));
-    i += e.mvfield.size() * sizeof(int16_t);
-    if (e.ltr_slots_) {
-        memcpy(e.ltr_state.data(), i, e.ltr_state.size() * sizeof(ltr::LtrState));
-        i += e.ltr_state.size() * sizeof(ltr::LtrState);
-        for (int j = 0; j < e.ltr_slots_; j++)
-            for (int p = 0; p < 3; p++) {
-                memcpy(e.ltr_planes[j][p].data(), i, e.ltr_planes[j][p].size());
-                i += e.ltr_planes[j][p].size();
-            }
-    }
-    e.first_frame = !h.started;
-    e.set_qp(h.qp, h.paint_qp);
-    return 0;
+// After a state import. HEVC: the next POC is the picture state's frame_num (the GPU back end
+// codes POC from it).
+template <class Enc>
+void after_import(Enc&) {}
+void after_import(hevc::CpuHevcEncoder& e) {
+    std::vector<h264::StripeState> st(e.fe.g.num_slices + 1);
+    e.fe.ctl_.export_states(st.data());
+    e.poc = st.back().frame_num;
 }
 
+// CPU reference back end of one codec: Enc is its encoder, `ctor` its arguments after the configuration.
+template <class Enc>
 class CpuBackend : public EncoderBackend {
    public:
-    explicit CpuBackend(const h264::EncoderConfig& c) : enc_(c) {}
+    template <class... A>
+    explicit CpuBackend(const h264::EncoderConfig& c, A... ctor) : enc_(c, ctor...) {}
     void request_keyframe() override { enc_.request_keyframe(); }
     void set_qp(int qp, int paint_qp) override { enc_.set_qp(qp, paint_qp); }
-    void set_rate(int mode, int kbps) override { enc_.ctl_.set_rate(mode, kbps); }
+    void set_rate(int mode, int kbps) override { fe().ctl_.set_rate(mode, kbps); }
     int64_t rc_stats(int32_t* out, int n) override {
         const int k = n < (int)(sizeof(h264::RcState) / 4) ? n : (int)(sizeof(h264::RcState) / 4);
-        memcpy(out, &enc_.ctl_.rc(), (size_t)k * 4);
+        memcpy(out, &fe().ctl_.rc(), (size_t)k * 4);
         return k;
     }
     int set_overlay_image(int slot, const uint8_t* bgra, int w, int h) override {
-        enc_.set_overlay_image(slot, bgra, w, h);
+        fe().set_overlay_image(slot, bgra, w, h);
         return 0;
     }
     int set_overlay_pos(int slot, int on, int x, int y, int tdx, int tdy) override {
-        enc_.set_overlay_pos(slot, on, x, y, tdx, tdy);
+        fe().set_overlay_pos(slot, on, x, y, tdx, tdy);
         return 0;
     }
     int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
@@ -132,176 +121,50 @@ class CpuBackend : public EncoderBackend {
         return (int)packets_.size();
     }
     int encode_yuv(const h264::YuvInput& in, int on_device, uint16_t frame_id) override {
-        if (enc_.scaled_) { set_last_error("planar input cannot be resampled"); return -1; }
+        if (fe().scaled_) { set_last_error("planar input cannot be resampled"); return -1; }
         HostYuv h;
-        if (h.load(in, on_device, enc_.g.W, enc_.g.H) < 0) return -1;
-        enc_.yuv_in = h.in;
+        if (h.load(in, on_device, fe().g.W, fe().g.H) < 0) return -1;
+        fe().yuv_in = h.in;
         return encode(nullptr, 0, frame_id);
     }
     int64_t debug_buffer(const char* name, void* dst, int64_t cap) override {
-        const void* p = nullptr;
-        int64_t n = 0;
-        std::string s(name);
-        auto plane = [&](const std::vector<uint8_t>& v) { p = v.data(); n = (int64_t)v.size(); };
-        if (s == "src_y") plane(enc_.prev[0]);  // after finish_frame the source lives in prev
-        else if (s == "src_u") plane(enc_.prev[1]);
-        else if (s == "src_v") plane(enc_.prev[2]);
-        else if (s == "ref_y") plane(enc_.ref[0]);
-        else if (s == "ref_u") plane(enc_.ref[1]);
-        else if (s == "ref_v") plane(enc_.ref[2]);
-        else if (s == "ref1_y") plane(enc_.ref1[0]);
-        else if (s == "ltr_state") { p = enc_.ltr_state.data(); n = (int64_t)(enc_.ltr_state.size() * sizeof(ltr::LtrState)); }
-        else if (s == "ltr_task") { p = enc_.ltr_task.data(); n = (int64_t)(enc_.ltr_task.size() * sizeof(ltr::LtrTask)); }
-        else if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
-                 s[3] < '0' + enc_.ltr_slots_) plane(enc_.ltr_planes[s[3] - '0'][0]);
-        else if (s == "mbs") { p = enc_.mbs.data(); n = (int64_t)(enc_.mbs.size() * sizeof(h264::MbInfo)); }
-        else if (s == "coefs") { p = enc_.coefs.data(); n = (int64_t)(enc_.coefs.size() * 2); }
-        else if (s == "me") { p = enc_.me.data(); n = (int64_t)(enc_.me.size() * sizeof(h264::MeResult)); }
-        else if (s == "tasks") { p = enc_.tasks.data(); n = (int64_t)(enc_.tasks.size() * sizeof(h264::SliceTask)); }
-        else if (s == "mb_dirty") plane(enc_.mb_dirty);
-        else if (s == "aq") { p = enc_.aq.data(); n = (int64_t)enc_.aq.size(); }
-        else if (s == "fs_mv") { p = enc_.fs_mv.data(); n = (int64_t)(enc_.fs_mv.size() * 2); }
-        else return -1;
-        if (dst && cap >= n) memcpy(dst, p, (size_t)n);
-        return n;
+        const std::string s(name);
+        const size_t plane = s.size() == 5 ? std::string("yuv").find(s[4]) : std::string::npos;   // "src_y": 0
+        DebugBuf b;
+        if (plane < 3 && s.compare(0, 4, "src_") == 0) b = bytes_of(fe().prev[plane]);   // after finish_frame the source lives in prev
+        else if (plane < 3 && s.compare(0, 4, "ref_") == 0) b = bytes_of(fe().ref[plane]);
+        else if (s == "me") b = bytes_of(fe().me);
+        else if (s == "tasks") b = bytes_of(fe().tasks);
+        else b = codec_debug(enc_, s);
+        if (b.second < 0) return -1;
+        if (dst && cap >= b.second) memcpy(dst, b.first, (size_t)b.second);
+        return b.second;
     }
 
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(enc_.g, enc_.ltr_slots_); }
-    int export_state(void* dst, int on_device) override { return cpu_export_state(enc_, dst, on_device); }
-    int import_state(const void* src, int on_device) override { return cpu_import_state(enc_, src, on_device); }
-
-   private:
-    h264::CpuH264Encoder enc_;
-};
-
-class CpuHevcBackend : public EncoderBackend {
-   public:
-    explicit CpuHevcBackend(const h264::EncoderConfig& c) : enc_(c) {}
-    void request_keyframe() override { enc_.request_keyframe(); }
-    void set_qp(int qp, int paint_qp) override { enc_.set_qp(qp, paint_qp); }
-    void set_rate(int mode, int kbps) override { enc_.fe.ctl_.set_rate(mode, kbps); }
-    int64_t rc_stats(int32_t* out, int n) override {
-        const int k = n < (int)(sizeof(h264::RcState) / 4) ? n : (int)(sizeof(h264::RcState) / 4);
-        memcpy(out, &enc_.fe.ctl_.rc(), (size_t)k * 4);
-        return k;
+    int64_t state_bytes() override {   // the long-term cache is H.264's alone
+        if constexpr (std::is_same<Enc, h264::CpuH264Encoder>::value)
+            return (int64_t)h264::state_bytes(enc_.g, enc_.ltr_slots_);
+        else
+            return (int64_t)h264::state_bytes(fe().g);
     }
-    int set_overlay_image(int slot, const uint8_t* bgra, int w, int h) override {
-        enc_.fe.set_overlay_image(slot, bgra, w, h);
+    int export_state(void* dst, int on_device) override {
+        if (on_device) return -1;
+        h264::cpu_export_state(fe(), dst);
         return 0;
     }
-    int set_overlay_pos(int slot, int on, int x, int y, int tdx, int tdy) override {
-        enc_.fe.set_overlay_pos(slot, on, x, y, tdx, tdy);
-        return 0;
-    }
-    int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
-        packets_.clear();
-        enc_.encode(bgrx, stride, frame_id, packets_);
-        return (int)packets_.size();
-    }
-    int encode_yuv(const h264::YuvInput& in, int on_device, uint16_t frame_id) override {
-        if (enc_.fe.scaled_) { set_last_error("planar input cannot be resampled"); return -1; }
-        HostYuv h;
-        if (h.load(in, on_device, enc_.fe.g.W, enc_.fe.g.H) < 0) return -1;
-        enc_.fe.yuv_in = h.in;
-        return encode(nullptr, 0, frame_id);
-    }
-    int64_t debug_buffer(const char* name, void* dst, int64_t cap) override {
-        const void* p = nullptr;
-        int64_t n = 0;
-        std::string s(name);
-        auto plane = [&](const std::vector<uint8_t>& v) { p = v.data(); n = (int64_t)v.size(); };
-        if (s == "src_y") plane(enc_.fe.prev[0]);
-        else if (s == "src_u") plane(enc_.fe.prev[1]);
-        else if (s == "src_v") plane(enc_.fe.prev[2]);
-        else if (s == "ref_y") plane(enc_.fe.ref[0]);
-        else if (s == "ref_u") plane(enc_.fe.ref[1]);
-        else if (s == "ref_v") plane(enc_.fe.ref[2]);
-        else if (s == "cus") { p = enc_.cus.data(); n = (int64_t)(enc_.cus.size() * sizeof(hevc::CuInfo)); }
-        else if (s == "sao") { p = enc_.sao.data(); n = (int64_t)(enc_.sao.size() * sizeof(hevc::SaoParams)); }
-        else if (s == "coefs") { p = enc_.coefs.data(); n = (int64_t)(enc_.coefs.size() * 2); }
-        else if (s == "bin_n") { p = enc_.bin_n.data(); n = (int64_t)(enc_.bin_n.size() * 4); }
-        else if (s == "pc_dbg") { p = enc_.pc_dbg_.data(); n = (int64_t)(enc_.pc_dbg_.size() * 4); }
-        else if (s == "me") { p = enc_.fe.me.data(); n = (int64_t)(enc_.fe.me.size() * sizeof(h264::MeResult)); }
-        else if (s == "tasks") { p = enc_.fe.tasks.data(); n = (int64_t)(enc_.fe.tasks.size() * sizeof(h264::SliceTask)); }
-        else return -1;
-        if (dst && cap >= n) memcpy(dst, p, (size_t)n);
-        return n;
-    }
-
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(enc_.fe.g); }
-    int export_state(void* dst, int on_device) override { return cpu_export_state(enc_.fe, dst, on_device); }
     int import_state(const void* src, int on_device) override {
-        if (cpu_import_state(enc_.fe, src, on_device) < 0) return -1;
-        // the next POC: the picture state's frame_num (the GPU back end codes POC from it)
-        std::vector<h264::StripeState> st(enc_.fe.g.num_slices + 1);
-        enc_.fe.ctl_.export_states(st.data());
-        enc_.poc = st.back().frame_num;
+        if (on_device) return -1;
+        if (!h264::cpu_import_state(fe(), src)) {
+            set_last_error("encoder state does not match this encoder's geometry / codec");
+            return -1;
+        }
+        after_import(enc_);
         return 0;
     }
 
    private:
-    hevc::CpuHevcEncoder enc_;
-};
-
-class CpuAv1Backend : public EncoderBackend {
-   public:
-    explicit CpuAv1Backend(const h264::EncoderConfig& c) : enc_(c, c.tile_cols_log2, c.tile_rows_log2) {}
-    void request_keyframe() override { enc_.request_keyframe(); }
-    void set_qp(int qp, int paint_qp) override { enc_.set_qp(qp, paint_qp); }
-    void set_rate(int mode, int kbps) override { enc_.fe.ctl_.set_rate(mode, kbps); }
-    int64_t rc_stats(int32_t* out, int n) override {
-        const int k = n < (int)(sizeof(h264::RcState) / 4) ? n : (int)(sizeof(h264::RcState) / 4);
-        memcpy(out, &enc_.fe.ctl_.rc(), (size_t)k * 4);
-        return k;
-    }
-    int set_overlay_image(int slot, const uint8_t* bgra, int w, int h) override {
-        enc_.fe.set_overlay_image(slot, bgra, w, h);
-        return 0;
-    }
-    int set_overlay_pos(int slot, int on, int x, int y, int tdx, int tdy) override {
-        enc_.fe.set_overlay_pos(slot, on, x, y, tdx, tdy);
-        return 0;
-    }
-    int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
-        packets_.clear();
-        enc_.encode(bgrx, stride, frame_id, packets_);
-        return (int)packets_.size();
-    }
-    int encode_yuv(const h264::YuvInput& in, int on_device, uint16_t frame_id) override {
-        if (enc_.fe.scaled_) { set_last_error("planar input cannot be resampled"); return -1; }
-        HostYuv h;
-        if (h.load(in, on_device, enc_.fe.g.W, enc_.fe.g.H) < 0) return -1;
-        enc_.fe.yuv_in = h.in;
-        return encode(nullptr, 0, frame_id);
-    }
-    int64_t debug_buffer(const char* name, void* dst, int64_t cap) override {
-        const void* p = nullptr;
-        int64_t n = 0;
-        std::string s(name);
-        auto plane = [&](const std::vector<uint8_t>& v) { p = v.data(); n = (int64_t)v.size(); };
-        if (s == "src_y") plane(enc_.fe.prev[0]);
-        else if (s == "src_u") plane(enc_.fe.prev[1]);
-        else if (s == "src_v") plane(enc_.fe.prev[2]);
-        else if (s == "ref_y") plane(enc_.fe.ref[0]);
-        else if (s == "ref_u") plane(enc_.fe.ref[1]);
-        else if (s == "ref_v") plane(enc_.fe.ref[2]);
-        else if (s == "blk") { p = enc_.blk.data(); n = (int64_t)(enc_.blk.size() * sizeof(av1::BlkInfo)); }
-        else if (s == "levels") { p = enc_.lev.data(); n = (int64_t)(enc_.lev.size() * 2); }
-        else if (s == "me") { p = enc_.fe.me.data(); n = (int64_t)(enc_.fe.me.size() * sizeof(h264::MeResult)); }
-        else if (s == "tasks") { p = enc_.fe.tasks.data(); n = (int64_t)(enc_.fe.tasks.size() * sizeof(h264::SliceTask)); }
-        else if (s == "av1_geo") { p = &enc_.geo; n = (int64_t)sizeof(av1::Av1Geo); }
-        else if (s == "av1_qidx") { p = &enc_.fp.qidx; n = 4; }
-        else return -1;
-        if (dst && cap >= n) memcpy(dst, p, (size_t)n);
-        return n;
-    }
-
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(enc_.fe.g); }
-    int export_state(void* dst, int on_device) override { return cpu_export_state(enc_.fe, dst, on_device); }
-    int import_state(const void* src, int on_device) override { return cpu_import_state(enc_.fe, src, on_device); }
-
-   private:
-    av1::CpuAv1Encoder enc_;
+    h264::CpuH264Encoder& fe() { return front(enc_); }
+    Enc enc_;
 };
 
 class CpuJpegBackend : public EncoderBackend {
@@ -324,9 +187,9 @@ class CpuJpegBackend : public EncoderBackend {
 EncoderBackend* create_cpu_jpeg_backend(const jpeg::JpegConfig& c) { return new CpuJpegBackend(c); }
 
 EncoderBackend* create_cpu_backend(const h264::EncoderConfig& c) {
-    if (c.codec == 1) return new CpuHevcBackend(c);
-    if (c.codec == 2) return new CpuAv1Backend(c);
-    return new CpuBackend(c);
+    if (c.codec == 1) return new CpuBackend<hevc::CpuHevcEncoder>(c);
+    if (c.codec == 2) return new CpuBackend<av1::CpuAv1Encoder>(c, c.tile_cols_log2, c.tile_rows_log2);
+    return new CpuBackend<h264::CpuH264Encoder>(c);
 }
 
 h264::EncoderConfig to_config(const sk_h264_config* c) {

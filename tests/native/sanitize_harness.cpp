@@ -72,6 +72,37 @@ int main() {
             for (auto& p : out) bytes += p.data.size();
         }
     }
+    // session state round trip (h264_state.h), long-term cache off and with two slots: two frames,
+    // export, import into a second encoder, then a third frame on both gives the same packets
+    for (int slots = 0; slots <= 2; slots += 2) {
+        sk::h264::EncoderConfig c;
+        c.width = 130;
+        c.height = 70;
+        c.stripe_height = 32;
+        c.ltr_slots = slots;
+        sk::h264::CpuH264Encoder a(c), b(c);
+        std::vector<uint8_t> f((size_t)c.width * c.height * 4);
+        std::vector<sk::h264::EncodedPacket> oa, ob;
+        for (int t = 0; t < 2; t++) {
+            fill(f, c.width, c.height, t, 0);
+            oa.clear();
+            a.encode(f.data(), c.width * 4, (uint16_t)t, oa);
+        }
+        std::vector<uint8_t> blob(sk::h264::state_bytes(a.g, a.ltr_slots_));
+        sk::h264::cpu_export_state(a, blob.data());
+        bool same = sk::h264::cpu_import_state(b, blob.data());
+        fill(f, c.width, c.height, 2, 0);
+        oa.clear();
+        a.encode(f.data(), c.width * 4, 2, oa);
+        b.encode(f.data(), c.width * 4, 2, ob);
+        same = same && oa.size() == ob.size() && !oa.empty();
+        for (size_t i = 0; same && i < oa.size(); i++) same = oa[i].data == ob[i].data && !ob[i].key;
+        if (!same) {
+            printf("state round trip (ltr_slots %d): packets differ\n", slots);
+            return 1;
+        }
+        for (auto& p : ob) bytes += p.data.size();
+    }
     // telephony codecs
     std::vector<int16_t> pcm(3200), back(3200);
     for (int i = 0; i < 3200; i++) pcm[i] = (int16_t)((i * 977) % 65536 - 32768);

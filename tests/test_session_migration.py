@@ -1,4 +1,4 @@
-"""Session state transfer (codec/h264_encoder.h StateHeader; parallel/migrate.py).
+"""Session state transfer (codec/h264_state.h StateHeader; parallel/migrate.py).
 
 A session exported after frame k and imported into a fresh encoder must produce
 byte-identical packets from frame k+1 on — P frames, no IDR — in-process and
