@@ -37,6 +37,8 @@ CpuH264Encoder::CpuH264Encoder(const EncoderConfig& c) : cfg(c) {
     fs_mv.assign((size_t)g.num_mbs() * 2, 0);
     tasks.assign(g.num_slices, SliceTask());
     ltr_slots_ = ltr_slots_of(cfg);
+    ltr_excl_ = ltr_slots_ > 0 && cfg.codec == 1;
+    ltr_max_age_ = ltr_max_age_env();
     if (ltr_slots_) {
         for (int j = 0; j < ltr_slots_; j++)
             for (int p = 0; p < 3; p++) ltr_planes[j][p].assign(p ? nc : ny, 0);
@@ -187,7 +189,7 @@ void CpuH264Encoder::full_search(int mbx, int mby, const SliceTask& t, int16_t* 
     static thread_local int win[kFsWin][kFsWin];
     int sb[16][16];
     for (int wy = 0; wy < kFsWin; wy++) {
-        const uint8_t* row = &ref[0][(size_t)sk_clip(mby * 16 - kFsR + wy, y_lo, y_hi) * g.stride_y];
+        const uint8_t* row = &refs(0, t)[0][(size_t)sk_clip(mby * 16 - kFsR + wy, y_lo, y_hi) * g.stride_y];
         for (int wx = 0; wx < kFsWin; wx++) win[wy][wx] = (int)row[sk_clip(mbx * 16 - kFsR + wx, 0, x_hi)] - 128;
     }
     for (int y = 0; y < 16; y++)
@@ -372,7 +374,8 @@ void CpuH264Encoder::decide_scenecut(int s) {
             ref1 += me[mby * g.mb_w + mbx].ref == 1;
         }
     if (t.allow_scenecut && inter > intra) t.final_action = ACT_I;
-    if (ltr_slots_) ltr_task[s].ref1_mbs = t.final_action == ACT_P ? ref1 : 0;   // the stream's cur_slot (ltr_commit)
+    if (ltr_excl_) ltr_task[s].ref1_mbs = ltr::ltr_exclusive_mbs(ltr_task[s], t.final_action == ACT_P, t.num_rows * g.mb_w);
+    else if (ltr_slots_) ltr_task[s].ref1_mbs = t.final_action == ACT_P ? ref1 : 0;   // the stream's cur_slot (ltr_commit)
 }
 
 // Long-term cache, once per frame between planning and motion search (k_ltr_match +
@@ -391,6 +394,7 @@ void CpuH264Encoder::ltr_plan() {
             key |= tasks[s].action == ACT_I;
         }
         planned_p = planned_p && !key;
+        if (ltr_excl_) ltr::ltr_expire(ltr_slots_, st, tasks[s0].frame_num, ltr_max_age_);
         if (planned_p && ltr::ltr_large(nd, n) && st.valid)
             for (int s = s0; s < s1; s++) {
                 if (tasks[s].action != ACT_P) continue;
@@ -408,7 +412,7 @@ void CpuH264Encoder::ltr_plan() {
         ltr::ltr_decide(ltr_slots_, st, nd, n, planned_p, tasks[s0].frame_num, kFrameNumMask, s0, s1,
                         [&](int s) { return tasks[s].action == ACT_P; }, ltr_sad.data(), ltr_task.data());
         for (int s = s0; s < s1; s++)
-            if (ltr_task[s].slot >= 0) tasks[s].num_refs = 2;   // [previous picture, the slot]
+            if (ltr_task[s].slot >= 0 && !ltr_excl_) tasks[s].num_refs = 2;   // [previous picture, the slot]
     };
     if (cfg.fullframe) decide(ltr_state[ns], 0, ns);
     else
@@ -888,7 +892,10 @@ void CpuH264Encoder::finish_frame() {
     for (int p = 0; p < 3; p++) prev[p].swap(src[p]);
     if (ltr_slots_) {
         const int ns = g.num_slices;
-        if (cfg.fullframe) {
+        if (ltr_excl_) {
+            ltr::ltr_commit_rps(ltr_slots_, ltr_state[ns], ctl_.picture_is_idr(tasks.data()), tasks[0].frame_num,
+                                g.num_mbs(), 0, ns, ltr_task.data());
+        } else if (cfg.fullframe) {
             ltr::ltr_commit(ltr_slots_, ltr_state[ns], true, ctl_.picture_is_idr(tasks.data()), tasks[0].frame_num,
                             g.num_mbs(), 0, ns, ltr_task.data());
         } else {

@@ -10,6 +10,7 @@
 //  * full-frame mode (encoder "x264enc"): one picture whose slices are the
 //    stripes, emitted as a single 0x04 packet with y = 0.
 #pragma once
+#include <stdlib.h>
 #include <string.h>
 #include <stdint.h>
 #include <vector>
@@ -17,6 +18,7 @@
 #include "h264_core.h"
 #include "ratecontrol.h"
 #include "ltr.h"
+#include "hevc_level.h"
 
 namespace sk {
 namespace h264 {
@@ -57,19 +59,31 @@ struct EncoderConfig {
     int subpel = 1;              // quarter-pel refinement of P vectors (K4c, H.264 and HEVC); AV1 keeps integer vectors
     int intra4x4 = 0;            // H.264 I slices may code MBs as I_NxN (nine 4x4 modes) where cheaper; off
                                  // by default like x264's ultrafast preset (partitions none)
-    int ltr_slots = 0;           // H.264 long-term reference cache (ltr.h): pictures kept per stream for content
+    int ltr_slots = 0;           // H.264 / HEVC long-term reference cache (ltr.h): pictures kept per stream for content
                                  // that comes back (window switches); 0 = off, 1..8; excludes num_refs > 1
 };
 
-// Long-term cache slots in force: H.264 only (HEVC / AV1 share this configuration and the front end).
+// Long-term cache slots in force: H.264 and HEVC (AV1 shares this configuration and the front end).
 inline int ltr_slots_of(const EncoderConfig& c) {
-    return c.codec == 0 && c.ltr_slots > 0 ? (c.ltr_slots < ltr::kLtrMaxSlots ? c.ltr_slots : ltr::kLtrMaxSlots) : 0;
+    return (c.codec == 0 || c.codec == 1) && c.ltr_slots > 0 ? (c.ltr_slots < ltr::kLtrMaxSlots ? c.ltr_slots : ltr::kLtrMaxSlots) : 0;
+}
+
+// HEVC cache expiry age in pictures (ltr.h ltr_expire): SK_HEVC_LTR_MAX_AGE=<n>, clipped to
+// 2..32768 (tests exercise expiry at small sizes); read once when an encoder is built.
+inline int ltr_max_age_env() {
+    const char* e = getenv("SK_HEVC_LTR_MAX_AGE");
+    return e && e[0] ? ltr::ltr_clip_max_age(atoi(e)) : ltr::kLtrMaxAge;
 }
 
 // Why a configuration cannot run the long-term cache (nullptr: it can, or the cache is off).
 inline const char* ltr_config_error(const EncoderConfig& c) {
-    if (c.codec != 0 || c.ltr_slots <= 0) return nullptr;
+    if ((c.codec != 0 && c.codec != 1) || c.ltr_slots <= 0) return nullptr;
     if (c.ltr_slots > ltr::kLtrMaxSlots) return "ltr_slots must be 0 (off) or 1..8";
+    if (c.codec == 1) {   // HEVC: current picture + previous picture + slots within some level's MaxDpbSize (A.4.2)
+        if (hevc::level_idc_for((c.width + 15) & ~15, (c.height + 15) & ~15, c.fps, 2 + c.ltr_slots) < 0)
+            return "ltr_slots: no H.265 level holds this picture size with that many long-term pictures (MaxDpbSize)";
+        return nullptr;
+    }
     if (c.num_refs > 1)
         return "ltr_slots > 0 cannot be combined with num_refs > 1: the cached picture takes the second reference "
                "list position";

@@ -141,7 +141,7 @@ CpuHevcEncoder::CpuHevcEncoder(const h264::EncoderConfig& cfg) : fe(front_config
     sao.assign(nc, SaoParams{});
     sao_cost.assign(nc, 0);
     sao_md.assign((size_t)nc * kSaoMd, 0);
-    build_parameter_sets(fe.g.W, fe.g.H, cfg.full_range, cfg.fps, param_sets);
+    build_parameter_sets(fe.g.W, fe.g.H, cfg.full_range, cfg.fps, param_sets, fe.ltr_slots_);
     seg_k = intra_seg_k(geo.ctb_w, geo.ctb_h);
 }
 
@@ -430,6 +430,7 @@ void CpuHevcEncoder::code_slice_inter(int s) {
     const SliceMap m = smap();
     const int qp = t.qp, W = geo.W16;
     const int lam_boost = fe.ctl_.rc().lam_boost;
+    const std::vector<uint8_t>* rp = fe.ref0(s);   // the previous picture, or the slot the slice matched (ltr.h)
     auto mv = [&](int ux, int uy, int* x, int* y) {
         *x = h264::me_qx(fe.me[uy * W + ux]);
         *y = h264::me_qy(fe.me[uy * W + ux]);
@@ -457,13 +458,13 @@ void CpuHevcEncoder::code_slice_inter(int s) {
                 load_cu_src(ux, uy, sy, sy + 256, sy + 320);
                 for (int y = 0; y < 16; y++)
                     for (int x = 0; x < 16; x++)
-                        pry[y * 16 + x] = (uint8_t)luma_mc_sample(fe.ref[0].data(), g.stride_y, geo.pic_w, geo.pic_h,
+                        pry[y * 16 + x] = (uint8_t)luma_mc_sample(rp[0].data(), g.stride_y, geo.pic_w, geo.pic_h,
                                                                   ux * 16 + x, uy * 16 + y, mvx, mvy);
                 for (int y = 0; y < 8; y++)
                     for (int x = 0; x < 8; x++) {
-                        pry[256 + y * 8 + x] = (uint8_t)chroma_mc_sample(fe.ref[1].data(), g.stride_c, g.stride_c,
+                        pry[256 + y * 8 + x] = (uint8_t)chroma_mc_sample(rp[1].data(), g.stride_c, g.stride_c,
                                                                          g.plane_h_c, ux * 8 + x, uy * 8 + y, mvx, mvy);
-                        pry[320 + y * 8 + x] = (uint8_t)chroma_mc_sample(fe.ref[2].data(), g.stride_c, g.stride_c,
+                        pry[320 + y * 8 + x] = (uint8_t)chroma_mc_sample(rp[2].data(), g.stride_c, g.stride_c,
                                                                          g.plane_h_c, ux * 8 + x, uy * 8 + y, mvx, mvy);
                     }
                 int16_t* lev = &coefs[(size_t)idx * kCoefPerCu];
@@ -880,6 +881,13 @@ std::vector<uint8_t> CpuHevcEncoder::write_segment(const SliceTask& t, int cy0, 
     h.qp_delta = t.qp - 26;
     h.num_entry = rows - 1;
     h.entry = esc.data();
+    if (fe.ltr_slots_) {   // long-term cache: the RPS of every slice, list 0 of a matched P slice
+        const ltr::LtrState& ls = fe.ltr_state[geo.num_slices];   // after this picture's expiry, before its commit
+        h.lt_present = 1;
+        h.lt_valid = ls.valid;
+        h.lt_poc = ls.st_fn;
+        h.lt_slot = p_slice ? fe.ltr_task[t.first_row / fe.g.rows_per_slice].slot : -1;
+    }
     const int hn = write_slice_header(hdr, h);
     std::vector<uint8_t> rbsp(hdr, hdr + hn);
     for (int r = 0; r < rows; r++) rbsp.insert(rbsp.end(), sub[r].begin(), sub[r].end());
@@ -912,6 +920,7 @@ void CpuHevcEncoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id,
         st.subpel_prev = st.subpel_hits;
         st.subpel_hits = 0;
     }
+    if (fe.ltr_slots_) fe.ltr_plan();   // long-term cache (ltr.h, exclusive mode): expiry, match, store
     const int ns = geo.num_slices;
     for (int s = 0; s < ns; s++)
         if (fe.tasks[s].action == ACT_P) {

@@ -83,9 +83,11 @@ inline int intra_seg_k(int ctb_w, int ctb_h) {
     return intra_seg_count(ctb_w, seg);
 }
 
-int choose_level_idc(int w, int h, float fps);
-// VPS + SPS + PPS NAL units (Annex B) for a w x h picture.
-void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<uint8_t>& out);
+// dpb_pics > 0: the level's MaxDpbSize must hold that many pictures (-1: none does), hevc_level.h
+int choose_level_idc(int w, int h, float fps, int dpb_pics = 0);
+// VPS + SPS + PPS NAL units (Annex B) for a w x h picture; ltr_slots > 0: long-term pictures
+// and list modification announced, the DPB sized for them.
+void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<uint8_t>& out, int ltr_slots = 0);
 // Start code + 2-byte NAL header + emulation-prevented RBSP.
 void append_nal(std::vector<uint8_t>& out, int type, const uint8_t* rbsp, size_t n);
 

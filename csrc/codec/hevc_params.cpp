@@ -1,25 +1,13 @@
 // H.265 parameter sets (VPS 7.3.2.1, SPS 7.3.2.2, PPS 7.3.2.3) for the coding
 // structure of hevc_core.h, NAL packaging and level selection (Annex A).
 #include "hevc_encoder.h"
+#include "hevc_level.h"
 #include <string.h>
 
 namespace sk {
 namespace hevc {
 
-int choose_level_idc(int w, int h, float fps) {
-    const double ps = (double)w * h, sr = ps * (fps > 0 ? fps : 60.0);
-    struct L { int idc; double ps, sr; };
-    static const L levels[] = {{30, 36864, 552960},          {60, 122880, 3686400},
-                               {63, 245760, 7372800},        {90, 552960, 16588800},
-                               {93, 983040, 33177600},       {120, 2228224, 66846720},
-                               {123, 2228224, 133693440},    {150, 8912896, 267386880},
-                               {153, 8912896, 534773760},    {156, 8912896, 1069547520},
-                               {180, 35651584, 1069547520},  {183, 35651584, 2139095040},
-                               {186, 35651584, 4278190080.0}};
-    for (const L& l : levels)
-        if (ps <= l.ps && sr <= l.sr) return l.idc;
-    return 186;
-}
+int choose_level_idc(int w, int h, float fps, int dpb_pics) { return level_idc_for(w, h, fps, dpb_pics); }
 
 static void profile_tier_level(HBitWriter& w, int level_idc) {
     w.put(0, 2);              // general_profile_space
@@ -46,9 +34,12 @@ void append_nal(std::vector<uint8_t>& out, int type, const uint8_t* rbsp, size_t
     out.resize(o + (size_t)m);
 }
 
-void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<uint8_t>& out) {
+void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<uint8_t>& out, int ltr_slots) {
     const int pw = (w + 15) & ~15, ph = (h + 15) & ~15;
-    const int level = choose_level_idc(pw, ph, fps);
+    // long-term cache (ltr.h): the DPB holds the current picture, the previous one and the slots
+    const int lvl = choose_level_idc(pw, ph, fps, ltr_slots > 0 ? 2 + ltr_slots : 0);
+    const int level = lvl < 0 ? 186 : lvl;   // ltr_config_error refuses such a session before it gets here
+    const uint32_t max_dec = ltr_slots > 0 ? 1 + (uint32_t)ltr_slots : 1;
     uint8_t buf[256];
     // ---- VPS ----
     memset(buf, 0, sizeof(buf));
@@ -63,7 +54,7 @@ void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<u
         v.put(0xffff, 16);    // vps_reserved_0xffff_16bits
         profile_tier_level(v, level);
         v.put1(1);            // vps_sub_layer_ordering_info_present_flag
-        v.ue(1);              // vps_max_dec_pic_buffering_minus1
+        v.ue(max_dec);        // vps_max_dec_pic_buffering_minus1
         v.ue(0);              // vps_max_num_reorder_pics
         v.ue(0);              // vps_max_latency_increase_plus1
         v.put(0, 6);          // vps_max_layer_id
@@ -99,7 +90,7 @@ void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<u
         s.ue(0);              // bit_depth_chroma_minus8
         s.ue(kLog2MaxPocLsb - 4);
         s.put1(1);            // sps_sub_layer_ordering_info_present_flag
-        s.ue(1);              // sps_max_dec_pic_buffering_minus1
+        s.ue(max_dec);        // sps_max_dec_pic_buffering_minus1
         s.ue(0);              // sps_max_num_reorder_pics
         s.ue(0);              // sps_max_latency_increase_plus1
         s.ue(0);              // log2_min_luma_coding_block_size_minus3: 8x8 (intra CU8s)
@@ -118,7 +109,8 @@ void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<u
         s.ue(0);              // num_positive_pics
         s.ue(0);              // delta_poc_s0_minus1
         s.put1(1);            // used_by_curr_pic_s0_flag
-        s.put1(0);            // long_term_ref_pics_present_flag
+        s.put1(ltr_slots > 0);   // long_term_ref_pics_present_flag
+        if (ltr_slots > 0) s.ue(0);   // num_long_term_ref_pics_sps: every entry is written in the slice header
         s.put1(0);            // sps_temporal_mvp_enabled_flag
         s.put1(0);            // strong_intra_smoothing_enabled_flag
         s.put1(1);            // vui_parameters_present_flag
@@ -140,7 +132,7 @@ void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<u
         s.put1(1);            // bitstream_restriction_flag
         s.put1(0);            // tiles_fixed_structure_flag
         s.put1(1);            // motion_vectors_over_pic_boundaries_flag
-        s.put1(1);            // restricted_ref_pic_lists_flag
+        s.put1(ltr_slots > 0 ? 0 : 1);   // restricted_ref_pic_lists_flag (cache: slices of a picture differ in list 0)
         s.ue(0);              // min_spatial_segmentation_idc
         s.ue(0);              // max_bytes_per_pic_denom
         s.ue(0);              // max_bits_per_min_cu_denom
@@ -182,7 +174,7 @@ void build_parameter_sets(int w, int h, int full_range, float fps, std::vector<u
         p.se(0);              // pps_beta_offset_div2
         p.se(0);              // pps_tc_offset_div2
         p.put1(0);            // pps_scaling_list_data_present_flag
-        p.put1(0);            // lists_modification_present_flag
+        p.put1(ltr_slots > 0);   // lists_modification_present_flag
         p.ue(0);              // log2_parallel_merge_level_minus2
         p.put1(0);            // slice_segment_header_extension_present_flag
         p.put1(0);            // pps_extension_present_flag

@@ -183,5 +183,62 @@ SK_HD void ltr_commit(int slots, LtrState& st, bool coded, bool idr, int frame_n
     st.st_fn[st.n_st++] = frame_num;
 }
 
+// ---- exclusive mode (HEVC) ----------------------------------------------------------
+// A matched slice predicts from its slot alone (reference index 0 of a one-entry list), so
+// the slice keeps one reference and every unit coded as P counts for the slot. An RPS names
+// every picture the decoder keeps, so no marking model is needed; the free fields hold
+// picture order counts instead: st_fn[j] = POC LSBs (16 bits) of slot j's picture, n_st = 1
+// once a previous picture exists (the store condition of ltr_decide), mmco1 stays -1.
+constexpr int kLtrPocMask = 0xffff;
+constexpr int kLtrMaxAge = 32768;   // default and upper bound of the expiry age
+
+SK_HD int ltr_clip_max_age(int n) { return n < 2 ? 2 : (n > kLtrMaxAge ? kLtrMaxAge : n); }
+
+// Expiry, at the start of a picture's decision (`poc`: its POC LSBs): a slot whose picture
+// is max_age or more pictures old leaves the cache. Checked on every coded picture, so no
+// age is stepped over and all POCs a decoder holds span less than 2^16: long-term entries
+// need no MSB.
+SK_HD void ltr_expire(int slots, LtrState& st, int poc, int max_age) {
+    for (int j = 0; j < slots; j++)
+        if (((st.valid >> j) & 1) && ((poc - st.st_fn[j]) & kLtrPocMask) >= max_age) {
+            st.valid &= ~(1 << j);
+            if (st.cur_slot == j) st.cur_slot = -1;
+        }
+}
+
+// ref1_mbs of a slice in exclusive mode: all of its `mbs` units when it matched a slot and
+// is coded as P.
+SK_HD int ltr_exclusive_mbs(const LtrTask& t, bool coded_p, int mbs) { return t.slot >= 0 && coded_p ? mbs : 0; }
+
+// ltr_commit for a stream whose pictures carry an RPS (`poc`: POC LSBs of the picture just
+// coded; the stored picture is the one before it). An IDR empties the cache.
+SK_HD void ltr_commit_rps(int slots, LtrState& st, bool idr, int poc, int mbs, int s0, int s1, const LtrTask* lt) {
+    if (idr) {
+        const int q = st.quiet_run;
+        ltr_state_reset(st);
+        st.quiet_run = q;
+        st.n_st = 1;
+        return;
+    }
+    const LtrTask& f = lt[s0];
+    if (f.flags & LTR_GATED) {
+        st.cur_slot = -1;
+        for (int j = slots - 1; j >= 0; j--) {
+            int cnt = 0;
+            for (int s = s0; s < s1; s++)
+                if (lt[s].slot == j) cnt += lt[s].ref1_mbs;
+            if (2 * cnt >= mbs) st.cur_slot = j;
+        }
+        if (st.cur_slot >= 0 && st.cur_slot == f.store_slot) st.cur_slot = -1;   // the slot now holds the previous content
+    } else if (f.flags & LTR_DRIFT) {
+        st.cur_slot = -1;
+    }
+    if (f.store_slot >= 0) {
+        st.valid |= 1 << f.store_slot;
+        st.st_fn[f.store_slot] = (poc - 1) & kLtrPocMask;
+    }
+    st.n_st = 1;
+}
+
 }  // namespace ltr
 }  // namespace sk

@@ -506,9 +506,11 @@ __device__ __forceinline__ int mb_activity(uint32_t sw) {
 // of kWinWords): with `big` it holds the filled +-kFsR window and SADs at vectors
 // inside it are read from there; other vectors (me_range reaches further) come from
 // global memory. Without it, or when the best predictor lies outside it, the small
-// window is filled around the best predictor for the diamond.
-__device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask& t, int idx, int mbx, int mby,
-                                             uint32_t sw, bool have_fs, int fsx, int fsy, uint32_t* win, bool big) {
+// window is filled around the best predictor for the diamond. refy: luma of the slice's
+// reference index 0 (ref0_planes).
+__device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask& t, const uint8_t* refy, int idx, int mbx,
+                                             int mby, uint32_t sw, bool have_fs, int fsx, int fsy, uint32_t* win,
+                                             bool big) {
     const int l = lane_id();
     if (t.action == ACT_I) {   // planned key frame: only the activity (K10's intra complexity)
         const int dev = mb_activity(sw);
@@ -520,7 +522,7 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
     const int R = a.me_range;
     MeWin wn{win, big ? kFsWinWords : kWinWords, big ? kFsR : -1, 0, 0};
     auto sad_lane = [&](int dx, int dy) {
-        return wn.has(dx, dy) ? win_sad_lane(wn, sw, dx, dy) : me_sad_lane(a, a.ref.y, sw, mbx, mby, dx, dy, ylo, yhi);
+        return wn.has(dx, dy) ? win_sad_lane(wn, sw, dx, dy) : me_sad_lane(a, refy, sw, mbx, mby, dx, dy, ylo, yhi);
     };
     // candidates (same order as the CPU reference): zero, the MB's own previous vector,
     // left, right, up, down, the exhaustive-search winner; a slot that does not exist
@@ -569,7 +571,7 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
         wave_sync();   // the reads of the big window are done
         const int r = l >> 1, h = l & 1;
         const int y = sk_clip(mby * 16 + by - kWin + r, ylo, yhi);
-        const uint8_t* rowp = a.ref.y + (size_t)y * a.stride_y;
+        const uint8_t* rowp = refy + (size_t)y * a.stride_y;
         const int x0 = mbx * 16 + bx - kWin + 16 * h;
 #pragma unroll
         for (int k = 0; k < 5; k++) win[r * kWinWords + 4 * h + k] = load_ref4(rowp, x0 + 4 * k, a.stride_y);
@@ -638,7 +640,7 @@ __global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
                                                      mbx * 16 + (l & 3) * 4);
     const bool have_fs = a.me_full && t.action == ACT_P && a.mb_dirty[idx];   // a winner left in fs_mv
     const int fsx = have_fs ? a.fs_mv[2 * idx] : 0, fsy = have_fs ? a.fs_mv[2 * idx + 1] : 0;
-    me_search_mb(a, t, idx, mbx, mby, sw, have_fs, fsx, fsy, win, false);
+    me_search_mb(a, t, ref0_planes(a, mby / a.rows_per_slice).y, idx, mbx, mby, sw, have_fs, fsx, fsy, win, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -670,8 +672,8 @@ constexpr int kFsSqInts = 2 * kFsR + 4;    // padded box-sum row stride (ints)
 
 // Fills the wave's window `win` and returns the minimum fs_key (the same in every lane).
 // The window stays valid afterwards.
-__device__ __forceinline__ uint64_t fs_search(const FrameArgs& a, uint32_t* win, uint32_t* blk, int* sq, int mbx, int mby,
-                                              uint32_t sw, int ylo, int yhi) {
+__device__ __forceinline__ uint64_t fs_search(const FrameArgs& a, const uint8_t* refy, uint32_t* win, uint32_t* blk, int* sq,
+                                              int mbx, int mby, uint32_t sw, int ylo, int yhi) {
     constexpr int WW = kFsWin / 4;                       // window dwords per row (12)
     constexpr int WP = kFsWinWords;                      // padded window row stride
     constexpr int BP = kFsBlkWords;
@@ -680,7 +682,7 @@ __device__ __forceinline__ uint64_t fs_search(const FrameArgs& a, uint32_t* win,
     for (int i = l; i < kFsWin * WW; i += 64) {
         const int wy = i / WW, q = i - wy * WW;
         const int y = sk_clip(mby * 16 - kFsR + wy, ylo, yhi);
-        win[wy * WP + q] = load_ref4(a.ref.y + (size_t)y * a.stride_y, mbx * 16 - kFsR + 4 * q, a.stride_y);
+        win[wy * WP + q] = load_ref4(refy + (size_t)y * a.stride_y, mbx * 16 - kFsR + 4 * q, a.stride_y);
     }
     blk[(l >> 2) * BP + (l & 3)] = sw;
     wave_sync();
@@ -803,6 +805,7 @@ __global__ __launch_bounds__(256) void k_me(FrameArgs a) {
     const int mbx = idx % a.mb_w, mby = idx / a.mb_w;
     const SliceTask t = a.tasks[mby / a.rows_per_slice];
     if (t.action != ACT_P && t.action != ACT_I) return;
+    const uint8_t* refy = ref0_planes(a, mby / a.rows_per_slice).y;   // wave-uniform
     const uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
                                                            mbx * 16 + (l & 3) * 4);
     bool have_fs = false, big = false;
@@ -812,12 +815,12 @@ __global__ __launch_bounds__(256) void k_me(FrameArgs a) {
         const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
         const int R = a.me_range;
         const int px = sk_clip(a.mvfield[2 * idx], -R, R), py = sk_clip(a.mvfield[2 * idx + 1], -R, R);
-        if (me_sad(a, a.ref.y, sw, mbx, mby, px, py, ylo, yhi) == 0) {
+        if (me_sad(a, refy, sw, mbx, mby, px, py, ylo, yhi) == 0) {
             // exact match at the MB's previous vector: skip the search (CPU: same rule)
             fsx = px;
             fsy = py;
         } else {
-            const uint64_t best = fs_search(a, win_s[w], blk_s[w], sq_s[w], mbx, mby, sw, ylo, yhi);
+            const uint64_t best = fs_search(a, refy, win_s[w], blk_s[w], sq_s[w], mbx, mby, sw, ylo, yhi);
             fsx = __builtin_amdgcn_readfirstlane(fs_key_dx(best));
             fsy = __builtin_amdgcn_readfirstlane(fs_key_dy(best));
             big = true;
@@ -827,7 +830,7 @@ __global__ __launch_bounds__(256) void k_me(FrameArgs a) {
             a.fs_mv[2 * idx + 1] = (int16_t)fsy;
         }
     }
-    me_search_mb(a, t, idx, mbx, mby, sw, have_fs, fsx, fsy, win_s[w], big);
+    me_search_mb(a, t, refy, idx, mbx, mby, sw, have_fs, fsx, fsy, win_s[w], big);
 }
 
 // Frame controller on the GPU (one workgroup): commits the previous frame's
@@ -845,7 +848,10 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
             for (int s = tid; s < ns; s += 256) idr &= a.tasks[s].final_action == ACT_I && a.tasks[s].idr_on_intra;
             idr = __syncthreads_and(idr);
             if (tid == 0) commit_picture(pic, idr, a.plan_cfg.num_refs);
-            if (a.ltr_slots && tid == 0)   // long-term cache: current slot and the marking model (ltr.h)
+            if (a.ltr_excl && tid == 0)   // HEVC: the cache follows the picture's RPS (ltr.h)
+                ltr::ltr_commit_rps(a.ltr_slots, a.ltr_state[ns], idr, a.tasks[0].frame_num, a.mb_w * a.mb_h, 0, ns,
+                                    a.ltr_task);
+            else if (a.ltr_slots && tid == 0)   // long-term cache: current slot and the marking model (ltr.h)
                 ltr::ltr_commit(a.ltr_slots, a.ltr_state[ns], true, idr, a.tasks[0].frame_num, a.mb_w * a.mb_h, 0, ns,
                                 a.ltr_task);
         } else {
@@ -973,11 +979,12 @@ __global__ __launch_bounds__(256) void k_ltr_decide(FrameArgs a) {
             anyp |= a.tasks[s].action == ACT_P;
             rows += a.tasks[s].num_rows;
         }
+        if (a.ltr_excl) ltr::ltr_expire(a.ltr_slots, a.ltr_state[ns], a.tasks[s0].frame_num, a.ltr_max_age);
         ltr::ltr_decide(a.ltr_slots, a.ltr_state[a.fullframe ? ns : k], a.ltr_cnt[2 * s0], rows * a.mb_w, anyp && !key,
                         a.tasks[s0].frame_num, kFrameNumMask, s0, s1,
                         [&](int s) { return a.tasks[s].action == ACT_P; }, a.ltr_sad, a.ltr_task);
         for (int s = s0; s < s1; s++)
-            if (a.ltr_task[s].slot >= 0) a.tasks[s].num_refs = 2;   // [previous picture, the slot]
+            if (a.ltr_task[s].slot >= 0 && !a.ltr_excl) a.tasks[s].num_refs = 2;   // [previous picture, the slot]
     }
 }
 
@@ -1017,7 +1024,9 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
         const long long ts = red[0][0] + red[0][1] + red[0][2] + red[0][3];
         const long long td = red[1][0] + red[1][1] + red[1][2] + red[1][3];
         t.final_action = (p && ts > td) ? ACT_I : t.action;
-        if (a.ltr_slots)
+        if (a.ltr_excl)
+            a.ltr_task[s].ref1_mbs = ltr::ltr_exclusive_mbs(a.ltr_task[s], planned_p && t.final_action == ACT_P, t.num_rows * a.mb_w);
+        else if (a.ltr_slots)
             a.ltr_task[s].ref1_mbs = (planned_p && t.final_action == ACT_P) ? red1[0] + red1[1] + red1[2] + red1[3] : 0;
         a.rc_slice[2 * s] = ts;       // K10 complexity (k_rc_qp)
         a.rc_slice[2 * s + 1] = td;
@@ -1873,7 +1882,7 @@ __global__ __launch_bounds__(256) void k_subpel(FrameArgs a) {
         return;
     }
     const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
-    qpel_fill_fast(Q, r.ref ? ref1_planes(a, sl).y : a.ref.y, a.stride_y, a.stride_y, ylo, yhi, mbx * 16 + r.mvx - 3,
+    qpel_fill_fast(Q, r.ref ? ref1_planes(a, sl).y : ref0_planes(a, sl).y, a.stride_y, a.stride_y, ylo, yhi, mbx * 16 + r.mvx - 3,
               mby * 16 + r.mvy - 3);
     const int yy = l >> 2, xx = 4 * (l & 3);
     const uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + yy) * a.stride_y +

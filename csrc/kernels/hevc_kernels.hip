@@ -610,6 +610,9 @@ __global__ __launch_bounds__(256) void k_hevc_inter(HevcArgs A) {
         return;
     }
     if (t.final_action != ACT_P) return;   // block-uniform
+    // the slice's reference: the previous picture, or the slot it matched (long-term cache);
+    // the slice is block-uniform, the base pointers are scalars
+    const Planes rp = h264::gpu::ref0_planes(f, r / A.rps);
     load_t16(T);
     for (int i = threadIdx.x; i < 1024; i += 256) T32[i] = HEVC_T32[i >> 5][i & 31];
     __syncthreads();
@@ -641,7 +644,7 @@ __global__ __launch_bounds__(256) void k_hevc_inter(HevcArgs A) {
             for (int i = l; i < 23 * 23; i += 64) {
                 const int rr = i / 23, cc = i - rr * 23;
                 win[rr * 24 + cc] =
-                    f.ref.y[(size_t)sk_clip(y0 + rr, 0, pic_h - 1) * f.stride_y + sk_clip(x0 + cc, 0, pic_w - 1)];
+                    rp.y[(size_t)sk_clip(y0 + rr, 0, pic_h - 1) * f.stride_y + sk_clip(x0 + cc, 0, pic_w - 1)];
             }
             wsync();
             for (int i = l; i < 23 * 16; i += 64) {
@@ -670,7 +673,7 @@ __global__ __launch_bounds__(256) void k_hevc_inter(HevcArgs A) {
             }
             // chroma: lane -> component l >> 5, row (l >> 2) & 7, 2 columns
             const int cc = l >> 5, rr = (l >> 2) & 7;
-            const uint8_t* plane = cc ? f.ref.v : f.ref.u;
+            const uint8_t* plane = cc ? rp.v : rp.u;
 #pragma unroll
             for (int k = 0; k < 2; k++) {
                 const int x = 2 * (l & 3) + k;
@@ -2021,7 +2024,7 @@ __global__ __launch_bounds__(64) void k_hevc_hdr(HevcArgs A) {
     __shared__ uint8_t hdr[1024];
     __shared__ int esc[256];
     __shared__ int offs[kMaxSegsPerSlice + 1];
-    __shared__ uint8_t shdr[64][48];
+    __shared__ uint8_t shdr[64][kSegHeaderMax];
     const FrameArgs& f = A.f;
     const int s = blockIdx.x;
     const SliceTask t = f.tasks[s];
@@ -2031,8 +2034,18 @@ __global__ __launch_bounds__(64) void k_hevc_hdr(HevcArgs A) {
     for (int i = l; i < f.num_slices; i += 64) idr &= f.tasks[i].final_action == ACT_I && f.tasks[i].idr_on_intra;
     idr = __syncthreads_and(idr);
     const int r0 = t.first_row >> 1, nr = ((t.first_row + t.num_rows + 1) >> 1) - r0;   // CTB rows
+    // long-term cache: the RPS every slice carries (state after this picture's expiry, before
+    // its commit in the next k_plan), list 0 of a matched P slice
+    auto lt_fields = [&](SliceHeader& h, bool p_slice) {
+        if (!f.ltr_slots) return;
+        const ltr::LtrState& ls = f.ltr_state[f.num_slices];
+        h.lt_present = 1;
+        h.lt_valid = ls.valid;
+        h.lt_poc = ls.st_fn;
+        h.lt_slot = p_slice ? f.ltr_task[s].slot : -1;
+    };
     auto seg_header = [&](int cy, int k, uint8_t* buf) {   // header RBSP of a row segment
-        for (int i = 0; i < 48; i++) buf[i] = 0;
+        for (int i = 0; i < kSegHeaderMax; i++) buf[i] = 0;
         SliceHeader h;
         h.address = cy * A.cw + m.x0(cy, k);
         h.first_slice = h.address == 0;
@@ -2043,6 +2056,7 @@ __global__ __launch_bounds__(64) void k_hevc_hdr(HevcArgs A) {
         h.qp_delta = t.qp - 26;
         h.num_entry = 0;
         h.entry = nullptr;
+        lt_fields(h, false);
         return write_slice_header(buf, h);
     };
     if (m.split(r0)) {
@@ -2099,6 +2113,7 @@ __global__ __launch_bounds__(64) void k_hevc_hdr(HevcArgs A) {
         h.qp_delta = t.qp - 26;
         h.num_entry = nr - 1;
         h.entry = esc;
+        lt_fields(h, h.slice_type == 1);
         const int hn = write_slice_header(hdr, h);
         const int hesc = ep_escape(hdr, hn, nullptr);
         int total = 6 + hesc;

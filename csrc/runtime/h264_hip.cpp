@@ -537,7 +537,9 @@ class HipBackend : public EncoderBackend {
         copy_now(lt.data(), args_.ltr_task, sizeof(ltr::LtrTask) * ns);
         const std::vector<SliceTask>& tasks = pc.tasks;
         if (!pc.commit) return ls;
-        if (cfg_.fullframe)
+        if (args_.ltr_excl)
+            ltr::ltr_commit_rps(slots, ls[ns], pc.idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
+        else if (cfg_.fullframe)
             ltr::ltr_commit(slots, ls[ns], true, pc.idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
         else
             for (int s = 0; s < ns; s++)
@@ -652,6 +654,8 @@ class HipBackend : public EncoderBackend {
         a.ref1 = make_planes();
         a.rec = make_planes();
         a.ltr_slots = ltr_slots_of(cfg_);
+        a.ltr_excl = a.ltr_slots > 0 && cfg_.codec == 1;   // HEVC: one reference per slice (ltr.h exclusive mode)
+        a.ltr_max_age = ltr_max_age_env();
         if (a.ltr_slots) {   // long-term cache (codec/ltr.h): slot plane sets, stream states, per-frame decisions
             const size_t ny = (size_t)g_.stride_y * g_.plane_h_y, nc = (size_t)g_.stride_c * g_.plane_h_c;
             a.ltr_ny = ny;
@@ -938,7 +942,7 @@ class HipBackend : public EncoderBackend {
         h.reg_steps = getenv("SK_HEVC_REG_STEPS") ? atoi(getenv("SK_HEVC_REG_STEPS")) : 1;
         h.pc_seg = getenv("SK_HEVC_PC_SEG") ? sk_max(atoi(getenv("SK_HEVC_PC_SEG")), 1) : 32;
         hevc_params_.clear();
-        hevc::build_parameter_sets(g_.W, g_.H, cfg_.full_range, cfg_.fps, hevc_params_);
+        hevc::build_parameter_sets(g_.W, g_.H, cfg_.full_range, cfg_.fps, hevc_params_, ltr_slots_of(cfg_));
     }
 
     // AV1 back-end buffers (av1_gpu.h): cells, levels, level contexts, token slots per

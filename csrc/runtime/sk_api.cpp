@@ -54,12 +54,17 @@ template <class V>
 DebugBuf bytes_of(const V& v) { return {v.data(), (int64_t)(v.size() * sizeof(*v.data()))}; }
 
 // The debug_buffer names of each codec's own buffers; the front end's are resolved by CpuBackend.
-DebugBuf codec_debug(h264::CpuH264Encoder& e, const std::string& s) {
-    if (s == "ref1_y") return bytes_of(e.ref1[0]);
+// The long-term cache's buffers live in the front end (H.264 and HEVC).
+DebugBuf ltr_debug(h264::CpuH264Encoder& e, const std::string& s) {
     if (s == "ltr_state") return bytes_of(e.ltr_state);
     if (s == "ltr_task") return bytes_of(e.ltr_task);
     if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
         s[3] < '0' + e.ltr_slots_) return bytes_of(e.ltr_planes[s[3] - '0'][0]);
+    return {nullptr, -1};
+}
+DebugBuf codec_debug(h264::CpuH264Encoder& e, const std::string& s) {
+    if (s == "ref1_y") return bytes_of(e.ref1[0]);
+    if (s.compare(0, 3, "ltr") == 0) return ltr_debug(e, s);
     if (s == "mbs") return bytes_of(e.mbs);
     if (s == "coefs") return bytes_of(e.coefs);
     if (s == "mb_dirty") return bytes_of(e.mb_dirty);
@@ -73,6 +78,7 @@ DebugBuf codec_debug(hevc::CpuHevcEncoder& e, const std::string& s) {
     if (s == "coefs") return bytes_of(e.coefs);
     if (s == "bin_n") return bytes_of(e.bin_n);
     if (s == "pc_dbg") return bytes_of(e.pc_dbg_);
+    if (s.compare(0, 3, "ltr") == 0) return ltr_debug(e.fe, s);
     return {nullptr, -1};
 }
 DebugBuf codec_debug(av1::CpuAv1Encoder& e, const std::string& s) {
@@ -141,12 +147,7 @@ class CpuBackend : public EncoderBackend {
         return b.second;
     }
 
-    int64_t state_bytes() override {   // the long-term cache is H.264's alone
-        if constexpr (std::is_same<Enc, h264::CpuH264Encoder>::value)
-            return (int64_t)h264::state_bytes(enc_.g, enc_.ltr_slots_);
-        else
-            return (int64_t)h264::state_bytes(fe().g);
-    }
+    int64_t state_bytes() override { return (int64_t)h264::state_bytes(fe().g, fe().ltr_slots_); }
     int export_state(void* dst, int on_device) override {
         if (on_device) return -1;
         h264::cpu_export_state(fe(), dst);
@@ -232,7 +233,7 @@ h264::EncoderConfig to_config(const sk_h264_config* c) {
         e.fullframe = 1;
         e.num_refs = 1;
         e.deblock = 0;
-        e.ltr_slots = 0;
+        if (e.codec == 2) e.ltr_slots = 0;   // the long-term cache is H.264 / HEVC only
     }
     return e;
 }

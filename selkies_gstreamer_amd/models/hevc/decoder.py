@@ -314,6 +314,105 @@ class Sps:
     strong_smoothing: bool = False
     scaling_list: bool = False
     long_term: bool = False
+    max_dec_pic_buffering_minus1: int = 0
+    lt_ref_pics_sps: list = None   # (lt_ref_pic_poc_lsb_sps, used_by_curr_pic_lt_sps_flag)
+
+
+# ---------------------------------------------------------------------------
+# Reference picture management (8.3.1, 8.3.2, 8.3.4), as pure functions over picture order
+# counts so that hand-built decoded picture buffers can exercise them.
+def pic_order_cnt(lsb: int, prev_lsb: int, prev_msb: int, log2_max_lsb: int) -> tuple:
+    """PicOrderCntVal of a non-IDR picture (8.3.1) from its slice_pic_order_cnt_lsb and the
+    previous TemporalId-0 picture's LSB / MSB; returns (PicOrderCntVal, PicOrderCntMsb)."""
+    max_lsb = 1 << log2_max_lsb
+    if lsb < prev_lsb and prev_lsb - lsb >= max_lsb // 2:
+        msb = prev_msb + max_lsb
+    elif lsb > prev_lsb and lsb - prev_lsb > max_lsb // 2:
+        msb = prev_msb - max_lsb
+    else:
+        msb = prev_msb
+    return msb + lsb, msb
+
+
+def parse_lt_rps(b: Bits, sps: Sps, poc_lsb: int) -> list:
+    """The long-term part of a slice header's RPS (7.3.6.1): a list of
+    (PocLsbLt or full POC delta info) entries as (poc_lsb_lt, used_by_curr, msb_present, delta_msb_cycle)."""
+    cand = sps.lt_ref_pics_sps or []
+    num_sps = b.ue() if cand else 0
+    num = b.ue()
+    if num_sps > len(cand):
+        raise BitstreamError("num_long_term_sps out of range")
+    out = []
+    cycle = 0
+    for i in range(num_sps + num):
+        if i < num_sps:
+            idx = b.u(max(0, (len(cand) - 1).bit_length())) if len(cand) > 1 else 0
+            if idx >= len(cand):
+                raise BitstreamError("lt_idx_sps out of range")
+            lsb, used = cand[idx]
+        else:
+            lsb, used = b.u(sps.log2_poc_lsb), b.u(1)
+        present = b.u(1)
+        if present:
+            d = b.ue()
+            cycle = d if i in (0, num_sps) else cycle + d   # DeltaPocMsbCycleLt (7-52)
+        out.append((lsb, used, present, cycle if present else 0))
+    del poc_lsb
+    return out
+
+
+def derive_rps(poc: int, st: list, lt: list, dpb: list, log2_max_lsb: int) -> dict:
+    """8.3.2: the five RPS lists of the current picture as POCs of pictures in `dpb`, a list of
+    (PicOrderCntVal, is_long_term). `st`: (delta_poc, used_by_curr) of the short-term RPS,
+    `lt`: parse_lt_rps entries. Long-term entries are resolved first (any reference picture,
+    by LSB or by full POC) and turn their pictures long-term; short-term entries then name
+    short-term pictures only. Raises BitstreamError when an entry names no picture."""
+    max_lsb = 1 << log2_max_lsb
+    r = {"st_curr_before": [], "st_curr_after": [], "st_foll": [], "lt_curr": [], "lt_foll": []}
+    is_lt = {q: l for q, l in dpb}
+    for lsb, used, present, cycle in lt:
+        if present:
+            full = poc - cycle * max_lsb - ((poc & (max_lsb - 1)) - lsb)
+            hit = [q for q in is_lt if q == full]
+        else:
+            hit = [q for q in is_lt if (q & (max_lsb - 1)) == lsb]
+        if not hit:
+            raise BitstreamError(f"long-term RPS entry (POC LSB {lsb}) names no picture in the DPB")
+        if len(hit) > 1:
+            raise BitstreamError(f"long-term RPS entry (POC LSB {lsb}) is ambiguous without an MSB")
+        r["lt_curr" if used else "lt_foll"].append(hit[0])
+    for q in r["lt_curr"] + r["lt_foll"]:
+        is_lt[q] = True
+    for delta, used in st:
+        q = poc + delta
+        if q not in is_lt or is_lt[q]:
+            raise BitstreamError(f"short-term RPS entry (POC {q}) names no short-term picture in the DPB")
+        r["st_foll" if not used else ("st_curr_before" if delta < 0 else "st_curr_after")].append(q)
+    return r
+
+
+def parse_list_modification(b: Bits, n_curr: int, num_ref: int):
+    """ref_pic_lists_modification() of a P slice (7.3.6.2), present when the PPS allows it and
+    NumPicTotalCurr > 1: list_entry_l0 (Ceil(Log2(NumPicTotalCurr)) bits each), or None."""
+    if n_curr <= 1 or not b.u(1):
+        return None
+    w = (n_curr - 1).bit_length()
+    return [b.u(w) for _ in range(num_ref)]
+
+
+def build_list0(rps: dict, num_ref: int, entries: list | None) -> list:
+    """8.3.4: RefPicList0 as POCs; `entries` = list_entry_l0 when
+    ref_pic_list_modification_flag_l0 is set, else None."""
+    temp = rps["st_curr_before"] + rps["st_curr_after"] + rps["lt_curr"]
+    n = len(temp)
+    if n == 0:
+        raise BitstreamError("P slice with an empty reference picture set")
+    if entries is None:
+        return [temp[i % n] for i in range(num_ref)]
+    for e in entries:
+        if e >= n:
+            raise BitstreamError(f"list_entry_l0 {e} out of range (NumPicTotalCurr {n})")
+    return [temp[e] for e in entries]
 
 
 @dataclass
@@ -347,8 +446,14 @@ class HevcDecoder:
     def __init__(self):
         self.sps: Sps | None = None
         self.pps: Pps | None = None
-        self.ref = None          # previous decoded picture (Y, U, V) for P slices
-        self.poc = 0
+        self.ref = None          # reference picture (Y, U, V) of the slice being decoded
+        self.poc = 0             # PicOrderCntVal of the current picture
+        # decoded picture buffer (streams with long_term_ref_pics_present_flag; others keep the
+        # previous picture alone): {"poc", "lt", "planes"} per reference picture
+        self.dpb = []
+        self.prev_lsb = self.prev_msb = 0   # prevTid0Pic (8.3.1)
+        self.last_rps = None     # RPS of the last picture started (tests)
+        self.last_list0 = None   # RefPicList0 (POCs) of the last P slice
         self.frames = []
         self.cur = None
 
@@ -378,7 +483,8 @@ class HevcDecoder:
         s.log2_poc_lsb = b.ue() + 4
         sub = b.u(1)
         for _ in range(0 if sub else msl, msl + 1):
-            b.ue(); b.ue(); b.ue()
+            s.max_dec_pic_buffering_minus1 = b.ue()
+            b.ue(); b.ue()
         s.log2_min_cb = b.ue() + 3
         s.log2_ctb = s.log2_min_cb + b.ue()
         s.log2_min_tb = b.ue() + 2
@@ -399,7 +505,7 @@ class HevcDecoder:
             s.st_rps.append(self._st_rps(b, i, s.st_rps))
         s.long_term = bool(b.u(1))
         if s.long_term:
-            raise NotImplementedError("long-term refs")
+            s.lt_ref_pics_sps = [(b.u(s.log2_poc_lsb), b.u(1)) for _ in range(b.ue())]
         s.tmvp = bool(b.u(1))
         s.strong_smoothing = bool(b.u(1))
         self.sps = s
@@ -497,6 +603,8 @@ class HevcDecoder:
             self._sao_filter()
         Y, U, V = self.cur["Y"], self.cur["U"], self.cur["V"]
         self.ref = (Y.copy(), U.copy(), V.copy())
+        if s.long_term:   # the picture joins the DPB as a short-term reference
+            self.dpb.append({"poc": self.poc, "lt": False, "planes": self.ref})
         self.cur = None
         cl, cr, ct, cb = s.crop
         return (Y[2 * ct:s.height - 2 * cb, 2 * cl:s.width - 2 * cr].copy(),
@@ -577,15 +685,23 @@ class HevcDecoder:
         if p.output_flag_present:
             b.u(1)
         idr = nut in (19, 20)
+        rps_key = None
         if not idr:
-            b.u(s.log2_poc_lsb)
+            poc_lsb = b.u(s.log2_poc_lsb)
             if not b.u(1):
-                self._st_rps(b, s.num_st_rps, s.st_rps)
+                st = self._st_rps(b, s.num_st_rps, s.st_rps)
             elif s.num_st_rps > 1:
-                b.u(max(1, (s.num_st_rps - 1).bit_length()))
+                st = s.st_rps[b.u(max(1, (s.num_st_rps - 1).bit_length()))]
+            else:
+                st = s.st_rps[0] if s.st_rps else []
+            if s.long_term:
+                lt = parse_lt_rps(b, s, poc_lsb)
+                rps_key = (poc_lsb, tuple(st), tuple(lt))
             if s.tmvp:
                 if b.u(1):
                     raise NotImplementedError("TMVP")
+        if s.long_term:
+            self._reference_pictures(first, idr, rps_key)
         sao_luma = sao_chroma = False
         if s.sao:
             sao_luma = bool(b.u(1))
@@ -596,7 +712,12 @@ class HevcDecoder:
         if slice_type == 1:
             if b.u(1):
                 num_ref = b.ue() + 1
-            if p.lists_modification:
+            if s.long_term:
+                n_curr = sum(len(self.cur["rps"][k]) for k in ("st_curr_before", "st_curr_after", "lt_curr"))
+                entries = parse_list_modification(b, n_curr, num_ref) if p.lists_modification else None
+                self.last_list0 = build_list0(self.cur["rps"], num_ref, entries)
+                self.ref = next(d["planes"] for d in self.dpb if d["poc"] == self.last_list0[0])
+            elif p.lists_modification:
                 raise NotImplementedError("list modification")
             cabac_init = b.u(1) if p.cabac_init_present else 0
             max_merge = 5 - b.ue()
@@ -648,6 +769,36 @@ class HevcDecoder:
                 for k in range(len(starts))]
         self._slice_data(addr, slice_type, qp, cabac_init, num_ref, max_merge, subs, wc, hc)
         return done
+
+    def _reference_pictures(self, first: bool, idr: bool, rps_key):
+        """Per slice of a stream with long-term pictures: POC (8.3.1) and the RPS (8.3.2) with the
+        first slice of a picture - every later slice must carry the same RPS syntax."""
+        s = self.sps
+        if not first:
+            if rps_key != self.cur["rps_key"]:
+                raise BitstreamError("slices of one picture disagree on their reference picture set")
+            return
+        self.cur["rps_key"] = rps_key
+        if idr:
+            self.dpb = []
+            self.poc = self.prev_lsb = self.prev_msb = 0
+            self.cur["rps"] = {"st_curr_before": [], "st_curr_after": [], "st_foll": [], "lt_curr": [], "lt_foll": []}
+            self.last_rps = self.cur["rps"]
+            return
+        poc_lsb, st, lt = rps_key
+        self.poc, msb = pic_order_cnt(poc_lsb, self.prev_lsb, self.prev_msb, s.log2_poc_lsb)
+        self.prev_lsb, self.prev_msb = poc_lsb, msb
+        if len(st) + len(lt) > s.max_dec_pic_buffering_minus1:
+            raise BitstreamError(f"the RPS holds {len(st) + len(lt)} pictures, sps_max_dec_pic_buffering_minus1 is "
+                                 f"{s.max_dec_pic_buffering_minus1}")
+        rps = derive_rps(self.poc, list(st), list(lt), [(d["poc"], d["lt"]) for d in self.dpb], s.log2_poc_lsb)
+        keep_lt = set(rps["lt_curr"] + rps["lt_foll"])
+        keep = keep_lt | set(rps["st_curr_before"] + rps["st_curr_after"] + rps["st_foll"])
+        self.dpb = [d for d in self.dpb if d["poc"] in keep]   # every other picture is unused for reference
+        for d in self.dpb:
+            d["lt"] = d["poc"] in keep_lt
+        self.cur["rps"] = rps
+        self.last_rps = rps
 
     # ---------------- slice data ----------------
     def _avail(self, xc, yc, xn, yn) -> bool:

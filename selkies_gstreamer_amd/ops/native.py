@@ -341,8 +341,8 @@ class H264Encoder:
                  aq_strength: float = 0.0, subpel: bool = True, intra4x4: bool = False,
                  tile_cols_log2: int = -1, tile_rows_log2: int = -1, rate_control: str = "cqp",
                  bitrate_kbps: int = 0, ltr_slots: int = 0):
-        """ltr_slots: H.264 long-term reference cache, pictures kept per stream (stripe, or the
-        picture in full-frame mode) for content that comes back, 0 = off, 1..8; not with
+        """ltr_slots: long-term reference cache (H.264 and HEVC), pictures kept per stream (stripe, or
+        the picture in full-frame mode) for content that comes back, 0 = off, 1..8; H.264: not with
         num_refs > 1. aq_strength: MB-level adaptive QP (h264_mb.h aq_offset), 1.0 = x264 aq-mode 1
         strength; 0 = constant QP per slice (x264 ultrafast behaviour). deblock: True / False,
         or "auto" (the slices coded at QP >= 34, h264_encoder.h slice_deblock)."""
@@ -592,7 +592,15 @@ class H264Encoder:
 class HevcEncoder(H264Encoder):
     """HEVC Main encoder session: full-frame pictures whose slices are stripes of whole
     32x32-CTB rows (WPP substreams), same front end as the H.264 encoder. Packets carry
-    the 10-byte stripe header + Annex-B (VPS/SPS/PPS on IDR)."""
+    the 10-byte stripe header + Annex-B (VPS/SPS/PPS on IDR).
+
+    ltr_slots = 1..8 keeps that many settled pictures as long-term references (csrc/codec/ltr.h):
+    when a window comes back, each slice of the first frame predicts from the cached picture it
+    matches (its only reference, with the full motion search) instead of being coded as a scene
+    cut. The SPS then announces `2 + ltr_slots` pictures and the level is the lowest whose
+    MaxDpbSize holds them; a size / slot combination no level holds is refused (8K: at most 4).
+    SK_HEVC_LTR_MAX_AGE=<n> (2..32768, read at construction) is the age in pictures at which a
+    cached picture expires. With ltr_slots = 0 every byte is what it was without the option."""
 
     def __init__(self, width: int, height: int, **kw):
         kw.pop("fullframe", None)

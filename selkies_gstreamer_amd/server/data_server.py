@@ -182,10 +182,11 @@ class Capture:
         self.size, self.fps = (0, 0), 60.0
 
 
-def _ltr_slots_from_env() -> int:
-    """SELKIES_H264_LTR_SLOTS: long-term reference pictures cached per H.264 stream (0 = off, at most 8)."""
+def _ltr_slots_from_env(name: str = "SELKIES_H264_LTR_SLOTS") -> int:
+    """SELKIES_H264_LTR_SLOTS / SELKIES_HEVC_LTR_SLOTS: long-term reference pictures cached per H.264
+    stream / per HEVC (x265enc) session (0 = off, at most 8). Each variable means its own codec only."""
     try:
-        return max(0, min(8, int(os.environ.get("SELKIES_H264_LTR_SLOTS", "0") or 0)))
+        return max(0, min(8, int(os.environ.get(name, "0") or 0)))
     except ValueError:
         return 0
 
@@ -882,8 +883,10 @@ class DataStreamingServer:
             cs.h264_aq_strength = max(0, min(64, int(self.settings.h264_aq_strength)))
             cs.h264_subpel = 0 if self.settings.h264_subpel[0] else -1
             cs.h264_intra4x4 = int(bool(self.settings.h264_intra4x4[0]))
-            # long-term reference cache (H.264 only; csrc/codec/ltr.h), 0 = off
-            cs.h264_ltr_slots = _ltr_slots_from_env() if cs.output_mode == 1 else 0
+            # long-term reference cache (csrc/codec/ltr.h), 0 = off: H.264 and HEVC, each from its own variable
+            # (h264_ltr_slots is the front end's field, like h264_crf)
+            cs.h264_ltr_slots = (_ltr_slots_from_env() if cs.output_mode == 1 else
+                                 _ltr_slots_from_env("SELKIES_HEVC_LTR_SLOTS") if cs.output_mode == 2 else 0)
         cs.use_paint_over_quality = int(bool(p["use_paint_over_quality"]))
         cs.paint_over_trigger_frames, cs.damage_block_threshold, cs.damage_block_duration = 15, 10, 20
         cs.use_cpu = int(bool(p["use_cpu"]))
