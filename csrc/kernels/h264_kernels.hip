@@ -463,16 +463,22 @@ __device__ __forceinline__ int me_sad(const FrameArgs& a, const uint8_t* refy, u
 //   small  +-kWin around the best predictor, 32 rows x 36 bytes in rows of kWinWords
 //          (the extra word serves the aligned-pair read of the last unaligned column)
 //   big    the +-kFsR window of the exhaustive search (k_me), centred on the zero
-//          vector, 48 rows x 48 bytes in rows of kFsWinWords
+//          vector: 48 rows x 48 bytes inside the workgroup's shared window (48 rows x
+//          96 bytes in rows of kFsWinWords, the macroblock of wave w starting at byte
+//          16 w). Its bytes are stored sign-biased (^ 0x80) for the matrix cores, so a
+//          SAD read flips them back (`bias`).
 constexpr int kWin = 8;
 constexpr int kWinWords = 10;               // words per LDS row (40 B)
-constexpr int kFsWinWords = kFsWin / 4 + 1; // big window: 12 words + 1 of padding (see k_me)
+constexpr int kFsGroup = 4;                 // macroblocks (waves) of a k_me workgroup, one MB row
+constexpr int kFsWinBytes = kFsWin + 16 * (kFsGroup - 1);   // shared window row (96 B)
+constexpr int kFsWinWords = kFsWinBytes / 4 + 1;            // 24 words + 1 of padding (see k_me)
 
 struct MeWin {
     const uint32_t* w;
     int stride;    // words per row
     int rad;       // < 0: no window yet
     int cx, cy;    // vector of the window centre
+    uint32_t bias; // XOR that turns a stored word into samples
     __device__ __forceinline__ bool has(int dx, int dy) const {
         return dx - cx >= -rad && dx - cx <= rad && dy - cy >= -rad && dy - cy <= rad;
     }
@@ -486,7 +492,7 @@ __device__ __forceinline__ uint32_t win_sad_lane(const MeWin& wn, uint32_t sw, i
     const uint32_t* w = wn.w + (row + dy - wn.cy + wn.rad) * wn.stride + (bc >> 2);
     const int sh = bc & 3;
     const uint32_t rw = sh ? __builtin_amdgcn_alignbyte(w[1], w[0], sh) : w[0];
-    return __builtin_amdgcn_sad_u8(sw, rw, 0u);
+    return __builtin_amdgcn_sad_u8(sw, rw ^ wn.bias, 0u);
 }
 
 // sum |Y - mean| of a 16x16 MB, one wave (lane: 4 samples of row l / 4)
@@ -502,15 +508,15 @@ __device__ __forceinline__ int mb_activity(uint32_t sw) {
 // K4 search of one macroblock of an ACT_P / ACT_I slice by one wave: predictors in the
 // order of the CPU reference, diamond refinement, activity, second-reference test and
 // the MeResult store. sw: this lane's source word; (fsx, fsy): the exhaustive-search
-// winner, a predictor when have_fs. `win` is the wave's LDS region (at least 32 rows
-// of kWinWords): with `big` it holds the filled +-kFsR window and SADs at vectors
-// inside it are read from there; other vectors (me_range reaches further) come from
-// global memory. Without it, or when the best predictor lies outside it, the small
-// window is filled around the best predictor for the diamond. refy: luma of the slice's
-// reference index 0 (ref0_planes).
+// winner, a predictor when have_fs. `bigw` is the macroblock's filled +-kFsR window
+// (rad < 0: there is none): SADs at vectors inside it are read from there; other vectors
+// (me_range reaches further) come from global memory. Without it, or when the best
+// predictor lies outside it, the small window is filled around the best predictor for
+// the diamond in `win`, LDS of this wave alone (32 rows of kWinWords). refy: luma of the
+// slice's reference index 0 (ref0_planes).
 __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask& t, const uint8_t* refy, int idx, int mbx,
                                              int mby, uint32_t sw, bool have_fs, int fsx, int fsy, uint32_t* win,
-                                             bool big) {
+                                             const MeWin& bigw) {
     const int l = lane_id();
     if (t.action == ACT_I) {   // planned key frame: only the activity (K10's intra complexity)
         const int dev = mb_activity(sw);
@@ -520,7 +526,8 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
     const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
     const int lam = lambda_for_qp(rc_me_qp(*a.rc, t.qp));
     const int R = a.me_range;
-    MeWin wn{win, big ? kFsWinWords : kWinWords, big ? kFsR : -1, 0, 0};
+    const bool big = bigw.rad >= 0;
+    MeWin wn = bigw;
     auto sad_lane = [&](int dx, int dy) {
         return wn.has(dx, dy) ? win_sad_lane(wn, sw, dx, dy) : me_sad_lane(a, refy, sw, mbx, mby, dx, dy, ylo, yhi);
     };
@@ -566,16 +573,17 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
         int c = sd[k] + lam * (sk_se_bits(4 * cx[k]) + sk_se_bits(4 * cy[k]));
         if (c < bcost) { bcost = c; bx = cx[k]; by = cy[k]; bsad = sd[k]; }
     }
+    STAMP(63, 7);
     if (!(big && wn.has(bx, by))) {
         // fill the small window around the best predictor: lane -> (row l>>1, 5 words)
-        wave_sync();   // the reads of the big window are done
+        wave_sync();
         const int r = l >> 1, h = l & 1;
         const int y = sk_clip(mby * 16 + by - kWin + r, ylo, yhi);
         const uint8_t* rowp = refy + (size_t)y * a.stride_y;
         const int x0 = mbx * 16 + bx - kWin + 16 * h;
 #pragma unroll
         for (int k = 0; k < 5; k++) win[r * kWinWords + 4 * h + k] = load_ref4(rowp, x0 + 4 * k, a.stride_y);
-        wn = MeWin{win, kWinWords, kWin, bx, by};
+        wn = MeWin{win, kWinWords, kWin, bx, by, 0u};
         wave_sync();
     }
     const int ddx[4] = {0, -1, 1, 0}, ddy[4] = {-1, 0, 0, 1};
@@ -604,6 +612,7 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
         if (nb < 0) break;
         bx += ddx[nb]; by += ddy[nb]; bcost = ncost; bsad = nsad;
     }
+    STAMP(63, 8);
     const int dev = mb_activity(sw);   // scene-cut intra estimate
     int refi = 0;
     if (t.num_refs > 1 && a.mb_dirty[idx]) {   // second reference at the zero vector (CPU: same rule)
@@ -624,6 +633,7 @@ __device__ __forceinline__ void me_search_mb(const FrameArgs& a, const SliceTask
         r.fx = r.fy = 0;
         a.me[idx] = r;  // per-slice sums are reduced in k_decide (no same-line atomics)
     }
+    STAMP(63, 9);
 }
 
 // K4 without the exhaustive search (me_full off): one single-wave workgroup per MB.
@@ -640,7 +650,8 @@ __global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
                                                      mbx * 16 + (l & 3) * 4);
     const bool have_fs = a.me_full && t.action == ACT_P && a.mb_dirty[idx];   // a winner left in fs_mv
     const int fsx = have_fs ? a.fs_mv[2 * idx] : 0, fsy = have_fs ? a.fs_mv[2 * idx + 1] : 0;
-    me_search_mb(a, t, ref0_planes(a, mby / a.rows_per_slice).y, idx, mbx, mby, sw, have_fs, fsx, fsy, win, false);
+    me_search_mb(a, t, ref0_planes(a, mby / a.rows_per_slice).y, idx, mbx, mby, sw, have_fs, fsx, fsy, win,
+                 MeWin{nullptr, 0, -1, 0, 0, 0u});
 }
 
 // ---------------------------------------------------------------------------
@@ -652,82 +663,108 @@ __global__ __launch_bounds__(64) void k_motion_search(FrameArgs a) {
 //   D[dxw][dyw] = sum_{r', c} W[r'][dxw + c] * S[(r', c)][dyw],  S[(r',c)][dyw] = s'[r' - dyw][c]
 // (zero outside the block): 2 (dx) x 2 (dy) tiles of v_mfma_i32_16x16x64_i8, K = 4
 // window rows x 16 columns per instruction, 8 of the 12 K steps per dy tile (the
-// others are all-zero in S) = 32 MFMAs per MB. A fragments are unaligned 16-byte
-// runs of a window row (5 LDS dwords + v_alignbyte), B fragments aligned block rows.
-// sum w'^2 per candidate comes from separable 16-tap box sums in LDS. The wave
-// min of fs_key gives the winner, which the search adds as a predictor.
+// others are all-zero in S) = 32 MFMAs per MB. sum w'^2 per candidate comes from
+// separable 16-tap box sums in LDS. The wave min of fs_key gives the winner, which the
+// search adds as a predictor.
+//
+// The four macroblocks of a workgroup are neighbours in one MB row, so their windows
+// are 48-byte runs of one 48 x 96 window at byte offsets 16 w, and sum w'^2 is one
+// table over its 80 candidate columns (wave w reads columns 16 w ... 16 w + 31): the
+// workgroup fills and sums them once. Window and block are stored sign-biased, so the
+// MFMA operands need no arithmetic beyond the byte alignment of the A fragments:
+//   A  9 dwords of a window row serve both dx tiles (2 x 4 v_alignbyte)
+//   B  S depends on r' - dyw alone: with 15 / 16 zero rows around the block in LDS
+//      the eight fragments of ks - 4 nt = 0..7 are one unconditional 16-byte read each
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 // LDS row strides are padded against bank conflicts (MI355X_MICROARCH.md §LDS lane
-// groups; modelled per access in tools/lds_bank_model.py): window rows 13 dwords (odd:
+// groups; modelled per access in tools/lds_bank_model.py): window rows 25 dwords (odd:
 // the box-sum row loads of 48 lanes and the A fragments' two rows per 32-lane group fall
-// on distinct banks), block rows 5 dwords (B fragments read ~17 different rows per
-// group), box-sum rows 36 ints (16-B aligned int4 stores of 8 consecutive lanes cover 32
-// distinct banks; the fs_key reads are int4 too). 1512 -> 584 modelled LDS cycles per MB.
+// on distinct banks), block rows 4 dwords (a B fragment is one ds_read_b128; the 16 rows
+// of a lane group are consecutive, so they cover the 64 banks once), box-sum rows 84
+// ints (16-B aligned int4 stores of 8 consecutive lanes cover 32 distinct banks; the
+// int4 fs_key reads take 2 cycles per lane group there, and the 88 ints that would free
+// them double the stores). Modelled LDS cycles per MB: 584 with a window per wave, 497
+// now (analyse_shared: 84 / 25; 80 / 24 unpadded gives 668).
 // The search's SAD reads (win_sad_lane: 8 rows x 4 dwords per 32-lane group) take 2 cycles
-// per group at 13 dwords, as they do in the small window at 10, and 1 at 12: 4 modelled
-// cycles per SAD against 48 saved on the row loads, so the odd stride stays.
-constexpr int kFsBlkWords = 5;             // padded block row stride
-constexpr int kFsSqInts = 2 * kFsR + 4;    // padded box-sum row stride (ints)
+// per group at an odd stride, as they do in the small window at 10, and 1 at 28, where
+// the row loads take 3: 40 modelled cycles per MB either way, so the odd stride stays.
+constexpr int kFsBlkRows = 15 + 16 + 16;               // zero rows, block, zero rows
+constexpr int kFsCols = 2 * kFsR + 16 * (kFsGroup - 1); // candidate columns of a workgroup (80)
+constexpr int kFsSqInts = kFsCols + 4;                 // padded box-sum row stride (ints)
+static_assert(kFsCols % kFsGroup == 0 && (kFsCols / kFsGroup) % 4 == 0, "row sums: one column run per wave, int4 stores");
 
-// Fills the wave's window `win` and returns the minimum fs_key (the same in every lane).
-// The window stays valid afterwards.
+// The exhaustive search of a workgroup (all 256 threads call it; it holds barriers).
+// Fills the shared window `win` (origin: byte mbx0 * 16 - kFsR of window row 0) and the
+// table `sq`; a wave with `search` then returns the minimum fs_key of the macroblock
+// mbx0 + w (the same in every lane), whose source word is sw. The window stays valid.
 __device__ __forceinline__ uint64_t fs_search(const FrameArgs& a, const uint8_t* refy, uint32_t* win, uint32_t* blk, int* sq,
-                                              int mbx, int mby, uint32_t sw, int ylo, int yhi) {
-    constexpr int WW = kFsWin / 4;                       // window dwords per row (12)
+                                              int mbx0, int mby, uint32_t sw, bool search, int ylo, int yhi) {
+    constexpr int WW = kFsWinBytes / 4;                  // window dwords per row (24)
     constexpr int WP = kFsWinWords;                      // padded window row stride
-    constexpr int BP = kFsBlkWords;
     constexpr int SP = kFsSqInts;
-    const int l = lane_id();
-    for (int i = l; i < kFsWin * WW; i += 64) {
+    constexpr int SEG = kFsCols / kFsGroup;              // row sums per wave and window row (20)
+    const int tid = threadIdx.x, w = tid >> 6, l = lane_id();
+    for (int i = tid; i < kFsWin * WW; i += 64 * kFsGroup) {
         const int wy = i / WW, q = i - wy * WW;
         const int y = sk_clip(mby * 16 - kFsR + wy, ylo, yhi);
-        win[wy * WP + q] = load_ref4(refy + (size_t)y * a.stride_y, mbx * 16 - kFsR + 4 * q, a.stride_y);
+        win[wy * WP + q] = load_ref4(refy + (size_t)y * a.stride_y, mbx0 * 16 - kFsR + 4 * q, a.stride_y) ^ 0x80808080u;
     }
-    blk[(l >> 2) * BP + (l & 3)] = sw;
-    wave_sync();
-    // |r_d|^2: 16-tap row box sums (lane = window row), then 16-tap column sums in
-    // place. Each lane loads its whole row / column into registers before it stores
-    // anything: no LDS read waits behind an earlier store (a read-modify-write
-    // sliding loop over LDS serialised ~60 round trips per wave).
+    if (search) {   // block rows 15..30 between zero rows
+        if (l < 60) blk[l] = 0u;
+        blk[31 * 4 + l] = 0u;
+        blk[(15 + (l >> 2)) * 4 + (l & 3)] = sw ^ 0x80808080u;
+    }
+    __syncthreads();
+    STAMP(63, 2);
+    // |r_d|^2: 16-tap row box sums (wave = run of SEG columns, lane = window row), then
+    // 16-tap column sums in place. Each lane loads its whole run into registers before it
+    // stores anything: no LDS read waits behind an earlier store.
     if (l < kFsWin) {
-        uint32_t rw[WW];
+        constexpr int NB = SEG + 15;                     // window bytes under the run (35)
+        uint32_t rw[(NB + 3) / 4];
 #pragma unroll
-        for (int q = 0; q < WW; q++) rw[q] = win[l * WP + q];
-        int sqv[kFsWin];
+        for (int q = 0; q < (NB + 3) / 4; q++) rw[q] = win[l * WP + (SEG / 4) * w + q];
+        int sqv[NB];
 #pragma unroll
-        for (int c = 0; c < kFsWin; c++) {
-            const int v = (int)((rw[c >> 2] >> (8 * (c & 3))) & 255) - 128;
+        for (int c = 0; c < NB; c++) {
+            const int v = (int)(int8_t)(rw[c >> 2] >> (8 * (c & 3)));
             sqv[c] = v * v;
         }
         int acc = 0;
 #pragma unroll
         for (int c = 0; c < 16; c++) acc += sqv[c];
-        int out[2 * kFsR];
+        int out[SEG];
         out[0] = acc;
 #pragma unroll
-        for (int x = 1; x < 2 * kFsR; x++) {
+        for (int x = 1; x < SEG; x++) {
             acc += sqv[x + 15] - sqv[x - 1];
             out[x] = acc;
         }
 #pragma unroll
-        for (int x = 0; x < 2 * kFsR; x += 4)
-            *reinterpret_cast<int4*>(&sq[l * SP + x]) = make_int4(out[x], out[x + 1], out[x + 2], out[x + 3]);
+        for (int x = 0; x < SEG; x += 4)
+            *reinterpret_cast<int4*>(&sq[l * SP + SEG * w + x]) = make_int4(out[x], out[x + 1], out[x + 2], out[x + 3]);
     }
-    wave_sync();
-    if (l < 2 * kFsR) {
-        int col[kFsWin];
+    __syncthreads();
+    STAMP(63, 3);
+    // column sums, two threads per column: candidate rows 0..15 from table rows 0..30 go
+    // to rows 0..15, candidate rows 16..31 from rows 16..46 go to rows 32..47, so neither
+    // thread stores to a row the other one loads
+    if (tid < 2 * kFsCols) {
+        const int h = tid >= kFsCols, c = tid - h * kFsCols;
+        int col[31];
 #pragma unroll
-        for (int r = 0; r < kFsWin; r++) col[r] = sq[r * SP + l];
+        for (int r = 0; r < 31; r++) col[r] = sq[(16 * h + r) * SP + c];
         int acc = 0;
 #pragma unroll
         for (int r = 0; r < 16; r++) acc += col[r];
 #pragma unroll
-        for (int dy = 0; dy < 2 * kFsR; dy++) {
-            sq[dy * SP + l] = acc;
-            acc += col[dy + 16] - col[dy];
+        for (int dy = 0; dy < 16; dy++) {
+            sq[(32 * h + dy) * SP + c] = acc;
+            if (dy < 15) acc += col[dy + 16] - col[dy];
         }
     }
+    STAMP(63, 4);
     // cross-correlation on MFMA: lane (i = l & 15, g = l >> 4)
     const int i16 = l & 15, g = l >> 4;
     v4i acc[2][2];
@@ -735,102 +772,114 @@ __device__ __forceinline__ uint64_t fs_search(const FrameArgs& a, const uint8_t*
     for (int mt = 0; mt < 2; mt++)
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) acc[mt][nt] = v4i{0, 0, 0, 0};
+    if (search) {
+        v4i bf[8];                                       // block row 4 k + g - i16 of K step k = ks - 4 nt
 #pragma unroll
-    for (int ks = 0; ks < kFsWin / 4; ks++) {
-        const int rr = 4 * ks + g;                       // window row of this lane's K group
-        v4i bf[2];
+        for (int k = 0; k < 8; k++) bf[k] = *reinterpret_cast<const v4i*>(&blk[(4 * k + g - i16 + 15) * 4]);
+        const uint32_t* wr0 = win + 4 * w + (i16 >> 2);  // first window column of candidate dxw: 16 w + 16 mt + i16
+        const int sh = i16 & 3;
 #pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            const int src = rr - (16 * nt + i16);        // block row feeding candidate row dyw
-            const bool in = src >= 0 && src < 16;
+        for (int ks = 0; ks < kFsWin / 4; ks++) {
+            const uint32_t* wr = wr0 + (4 * ks + g) * WP; // window row of this lane's K group
+            uint32_t w9[9];
 #pragma unroll
-            for (int q = 0; q < 4; q++) bf[nt][q] = in ? (int)(blk[(in ? src : 0) * BP + q] ^ 0x80808080u) : 0;
-        }
+            for (int q = 0; q < 9; q++) w9[q] = wr[q];
 #pragma unroll
-        for (int mt = 0; mt < 2; mt++) {
-            const int b0 = 16 * mt + i16;                // first window column of candidate dxw
-            const uint32_t* wr = win + rr * WP + (b0 >> 2);
-            const int sh = b0 & 3;
-            uint32_t w5[5];
+            for (int mt = 0; mt < 2; mt++) {
+                v4i af;
 #pragma unroll
-            for (int q = 0; q < 5; q++) w5[q] = wr[q];
-            v4i af;
+                for (int q = 0; q < 4; q++) af[q] = (int)__builtin_amdgcn_alignbyte(w9[4 * mt + q + 1], w9[4 * mt + q], sh);
 #pragma unroll
-            for (int q = 0; q < 4; q++) af[q] = (int)(__builtin_amdgcn_alignbyte(w5[q + 1], w5[q], sh) ^ 0x80808080u);
-#pragma unroll
-            for (int nt = 0; nt < 2; nt++)
-                if (ks >= 4 * nt && ks <= 4 * nt + 7)
-                    acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf[nt], acc[mt][nt], 0, 0, 0);
-        }
-    }
-    wave_sync();
-    // D[dxw = 16 mt + 4 g + reg][dyw = 16 nt + i16]
-    uint64_t best = ~0ull;
-#pragma unroll
-    for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            const int dyw = 16 * nt + i16;
-            const int4 sv = *reinterpret_cast<const int4*>(&sq[dyw * SP + 16 * mt + 4 * g]);
-            const int svr[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++) {
-                const int dxw = 16 * mt + 4 * g + reg;
-                const uint64_t k = fs_key(svr[reg] - 2 * acc[mt][nt][reg], dyw, dxw);
-                best = k < best ? k : best;
+                for (int nt = 0; nt < 2; nt++)
+                    if (ks >= 4 * nt && ks <= 4 * nt + 7)
+                        acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf[ks - 4 * nt], acc[mt][nt], 0, 0, 0);
             }
         }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t other = __shfl_xor(best, o);
-        best = other < best ? other : best;
     }
+    STAMP(63, 5);
+    __syncthreads();
+    // D[dxw = 16 mt + 4 g + reg][dyw = 16 nt + i16]
+    uint64_t best = ~0ull;
+    if (search) {
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int nt = 0; nt < 2; nt++) {
+                const int dyw = 16 * nt + i16;
+                const int4 sv = *reinterpret_cast<const int4*>(&sq[(32 * nt + i16) * SP + 16 * w + 16 * mt + 4 * g]);
+                const int svr[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    const int dxw = 16 * mt + 4 * g + reg;
+                    const uint64_t k = fs_key(svr[reg] - 2 * acc[mt][nt][reg], dyw, dxw);
+                    best = k < best ? k : best;
+                }
+            }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint64_t other = __shfl_xor(best, o);
+            best = other < best ? other : best;
+        }
+    }
+    STAMP(63, 6);
     return best;
 }
 
-// K4a + K4 in one dispatch (me_full on): four waves per workgroup, one macroblock each.
-// Phase 1, dirty MBs of P slices: the exhaustive search (skipped on an exact match at
-// the MB's previous vector); the winner stays in registers and goes to fs_mv (a
-// debug_buffer name of the CPU model). Phase 2, every MB of a P / I slice:
-// me_search_mb, which reads its SADs from the wave's phase-1 window where it can.
+// K4a + K4 in one dispatch (me_full on): four waves per workgroup, one macroblock each,
+// four neighbours of one MB row (grid: mb_h x ceil(mb_w / 4); the waves of a last group
+// past the row's end only help with the shared window). Phase 1, dirty MBs of P slices:
+// the exhaustive search (skipped on an exact match at the MB's previous vector, and
+// by the whole workgroup when no wave searches); the winner stays in registers and goes
+// to fs_mv (a debug_buffer name of the CPU model). Phase 2, every MB of a P / I slice:
+// me_search_mb, which reads its SADs from the phase-1 window where it can.
 __global__ __launch_bounds__(256) void k_me(FrameArgs a) {
-    __shared__ uint32_t win_s[4][kFsWin * kFsWinWords];       // raw reference window per wave
-    __shared__ uint32_t blk_s[4][16 * kFsBlkWords];           // raw 16x16 source block
-    __shared__ __align__(16) int sq_s[4][kFsWin * kFsSqInts]; // row box sums of w'^2, then |r_d|^2
-    static_assert(kFsWin * kFsWinWords >= 32 * kWinWords, "the small window lives in the wave's win_s region");
+    __shared__ uint32_t win_s[kFsWin * kFsWinWords];                     // sign-biased reference window
+    __shared__ __align__(16) int sq_s[kFsWin * kFsSqInts];               // row box sums of w'^2, then |r_d|^2
+    // per wave: the sign-biased 16x16 source block between its zero rows, read by the wave's
+    // MFMA loop only; after that the diamond's small window. 26304 B in all: 6 workgroups per CU
+    __shared__ __align__(16) uint32_t small_s[kFsGroup][32 * kWinWords];
+    static_assert(32 * kWinWords >= kFsBlkRows * 4 && (32 * kWinWords) % 4 == 0, "the block lives in the wave's small window");
     const int w = threadIdx.x >> 6, l = lane_id();
-    const int nmb = a.mb_w * a.mb_h;
-    const int idx = xcd_remap(blockIdx.x, gridDim.x) * 4 + w;
-    if (idx >= nmb) return;
-    const int mbx = idx % a.mb_w, mby = idx / a.mb_w;
+    const int gw = (a.mb_w + kFsGroup - 1) / kFsGroup;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int mby = b / gw, mbx0 = (b - mby * gw) * kFsGroup, mbx = mbx0 + w;
+    if (mby >= a.mb_h) return;
     const SliceTask t = a.tasks[mby / a.rows_per_slice];
-    if (t.action != ACT_P && t.action != ACT_I) return;
-    const uint8_t* refy = ref0_planes(a, mby / a.rows_per_slice).y;   // wave-uniform
-    const uint32_t sw = *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
-                                                           mbx * 16 + (l & 3) * 4);
-    bool have_fs = false, big = false;
+    if (t.action != ACT_P && t.action != ACT_I) return;                  // the whole workgroup: one slice
+    STAMP(63, 0);
+    const bool valid = mbx < a.mb_w;
+    const int idx = mby * a.mb_w + mbx;
+    const uint8_t* refy = ref0_planes(a, mby / a.rows_per_slice).y;       // block-uniform
+    const uint32_t sw = valid ? *reinterpret_cast<const uint32_t*>(a.src.y + (size_t)(mby * 16 + (l >> 2)) * a.stride_y +
+                                                                   mbx * 16 + (l & 3) * 4)
+                              : 0u;
+    const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
+    bool have_fs = false, search = false;
     int fsx = 0, fsy = 0;
-    if (t.action == ACT_P && a.mb_dirty[idx]) {
+    if (valid && t.action == ACT_P && a.mb_dirty[idx]) {
         have_fs = true;
-        const int ylo = t.pic_row0 * 16, yhi = (t.pic_row0 + t.pic_rows) * 16 - 1;
         const int R = a.me_range;
-        const int px = sk_clip(a.mvfield[2 * idx], -R, R), py = sk_clip(a.mvfield[2 * idx + 1], -R, R);
-        if (me_sad(a, refy, sw, mbx, mby, px, py, ylo, yhi) == 0) {
-            // exact match at the MB's previous vector: skip the search (CPU: same rule)
-            fsx = px;
-            fsy = py;
-        } else {
-            const uint64_t best = fs_search(a, refy, win_s[w], blk_s[w], sq_s[w], mbx, mby, sw, ylo, yhi);
+        fsx = sk_clip(a.mvfield[2 * idx], -R, R);
+        fsy = sk_clip(a.mvfield[2 * idx + 1], -R, R);
+        // exact match at the MB's previous vector: skip the search (CPU: same rule)
+        search = me_sad(a, refy, sw, mbx, mby, fsx, fsy, ylo, yhi) != 0;
+    }
+    const bool any = __syncthreads_or(search);
+    STAMP(63, 1);
+    if (any) {
+        const uint64_t best = fs_search(a, refy, win_s, small_s[w], sq_s, mbx0, mby, sw, search, ylo, yhi);
+        if (search) {
             fsx = __builtin_amdgcn_readfirstlane(fs_key_dx(best));
             fsy = __builtin_amdgcn_readfirstlane(fs_key_dy(best));
-            big = true;
-        }
-        if (l == 0) {
-            a.fs_mv[2 * idx] = (int16_t)fsx;
-            a.fs_mv[2 * idx + 1] = (int16_t)fsy;
         }
     }
-    me_search_mb(a, t, refy, idx, mbx, mby, sw, have_fs, fsx, fsy, win_s[w], big);
+    if (!valid) return;
+    if (have_fs && l == 0) {
+        a.fs_mv[2 * idx] = (int16_t)fsx;
+        a.fs_mv[2 * idx + 1] = (int16_t)fsy;
+    }
+    me_search_mb(a, t, refy, idx, mbx, mby, sw, have_fs, fsx, fsy, small_s[w],
+                 MeWin{win_s + 4 * w, kFsWinWords, search ? kFsR : -1, 0, 0, 0x80808080u});
 }
 
 // Frame controller on the GPU (one workgroup): commits the previous frame's
@@ -3507,7 +3556,7 @@ void launch_frontend(const FrameArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k_ltr_match, dim3(a.rows_per_slice, 1 + a.ltr_slots, a.num_slices), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_ltr_decide, dim3(1), dim3(256), 0, s, a);
     }
-    if (a.me_full) hipLaunchKernelGGL(k_me, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
+    if (a.me_full) hipLaunchKernelGGL(k_me, dim3(a.mb_h * ((a.mb_w + kFsGroup - 1) / kFsGroup)), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_motion_search, dim3(nmb), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_decide, dim3(a.num_slices), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_rc_qp, dim3(1), dim3(64), 0, s, a);

@@ -72,6 +72,63 @@ def analyse(S, WW, BS):
             c += cycles(ad, G32, 32, 1)
     out['sad_read_x10'] = (round(10*c/len(offs)), 10*2*2)
     return out
-for S, WW, BS in [(32,12,4),(36,12,4),(36,13,5),(44,13,5),(33,13,5),(40,13,5),(52,13,5),(36,12,5)]:
-    o = analyse(S, WW, BS)
-    print(S, WW, BS, {k: f"{v[0]}/{v[1]}" for k, v in o.items()}, 'total', sum(v[0] for v in o.values()))
+def analyse_shared(S, WW):
+    """k_me with one 48 x 96 window (rows of WW dwords) and one 48 x 80 box-sum table (rows of S
+    ints) per workgroup of four macroblocks, block rows of 4 dwords between zero rows. Every entry
+    is (modelled, conflict-free) LDS cycles of the whole workgroup; the total is divided by 4."""
+    out = {}
+    W4 = range(4)
+    # (a) window fill: thread i + 256 k stores win[wy*WW + q], wy = i / 24, q = i % 24
+    c = n = 0
+    for k in range(5):
+        for w in W4:
+            ad = {l: ((i // 24)*WW + i % 24) for l in range(64) for i in [256*k + 64*w + l] if i < 48*24}
+            c += cycles(ad, G32, 32, 1); n += 2 if ad else 0
+    out['win_fill_store'] = (c, n)
+    # (b) row loads of the box sums: wave w, lane l < 48 reads win[l*WW + 5w + q], q < 9
+    c = sum(cycles({l: l*WW + 5*w + q for l in range(48)}, G32, 32, 1) for w in W4 for q in range(9)); out['win_row_read'] = (c, 4*9*2)
+    # (c) int4 stores of the row sums: sq[l*S + 20w + x], x = 0, 4, .., 16
+    c = sum(cycles({l: l*S + 20*w + x for l in range(48)}, W128, 32, 4) for w in W4 for x in range(0, 20, 4)); out['sq_store_b128'] = (c, 4*5*6)
+    # (d) column sums: thread t < 160 (h = t / 80, c = t % 80) reads rows 16h + r, r < 31, writes rows 32h + dy, dy < 16
+    c = 0
+    for w in range(3):
+        th = [t for t in range(64*w, 64*w + 64) if t < 160]
+        c += sum(cycles({t % 64: (16*(t // 80) + r)*S + t % 80 for t in th}, G32, 32, 1) for r in range(31))
+        c += sum(cycles({t % 64: (32*(t // 80) + dy)*S + t % 80 for t in th}, G32, 32, 1) for dy in range(16))
+    out['sq_col_read_write'] = (c, 5*(31 + 16))
+    # (e) fs_key reads (b128): wave w, (32nt + i16)*S + 16w + 16mt + 4g
+    c = 0
+    for w in W4:
+        for mt in range(2):
+            for nt in range(2):
+                c += cycles({l: (32*nt + (l & 15))*S + 16*w + 16*mt + 4*(l >> 4) for l in range(64)}, G128, 64, 4)
+    out['fs_read_b128'] = (c, 4*4*4)
+    # (f) A fragments: rows 4ks + g, dwords 4w + (i16 >> 2) + q, q < 9 (both dx tiles)
+    c = 0
+    for w in W4:
+        for ks in range(12):
+            for q in range(9):
+                c += cycles({l: (4*ks + (l >> 4))*WW + 4*w + ((l & 15) >> 2) + q for l in range(64)}, G32, 32, 1)
+    out['A_frag'] = (c, 4*12*9*2)
+    # (g) B fragments (b128): padded block row 4k + g - i16 + 15, rows of 4 dwords
+    c = 4*sum(cycles({l: (4*k + (l >> 4) - (l & 15) + 15)*4 for l in range(64)}, G128, 64, 4) for k in range(8))
+    out['B_frag_b128'] = (c, 4*8*4)
+    # (h) one search SAD read of wave w (win_sad_lane), averaged over offsets: x 10 per MB
+    offs = [(ox, oy) for ox in range(-16, 17) for oy in (-16, 0, 5, 16)]
+    c = 0
+    for w in W4:
+        for ox, oy in offs:
+            for k in range(2):
+                ad = {l: ((l >> 2) + oy + 16)*WW + 4*w + (((l & 3)*4 + ox + 16) >> 2) + k for l in range(64)}
+                c += cycles(ad, G32, 32, 1)
+    out['sad_read_x10'] = (round(10*c/len(offs)), 4*10*2*2)
+    return out
+if __name__ == '__main__':
+    print('one window per wave (S, WW, BS):')
+    for S, WW, BS in [(32,12,4),(36,12,4),(36,13,5),(44,13,5),(33,13,5),(40,13,5),(52,13,5),(36,12,5)]:
+        o = analyse(S, WW, BS)
+        print(S, WW, BS, {k: f"{v[0]}/{v[1]}" for k, v in o.items()}, 'total', sum(v[0] for v in o.values()))
+    print('one window per workgroup (S, WW), cycles per MB = total / 4:')
+    for S, WW in [(80,24),(84,24),(84,25),(88,25),(92,25),(84,27),(84,28),(100,25)]:
+        o = analyse_shared(S, WW)
+        print(S, WW, {k: f"{v[0]}/{v[1]}" for k, v in o.items()}, 'per MB', sum(v[0] for v in o.values()) / 4)
