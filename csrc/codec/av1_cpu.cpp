@@ -118,8 +118,9 @@ void write_frame_header(BitWriter& w, const Av1Geo& g, const FrameParams& fp) {
     w.put(0, 1);                        // frame_size_override_flag
     if (!fp.key) {
         w.put(7, 3);                    // primary_ref_frame = PRIMARY_REF_NONE
-        w.put(0x01, 8);                 // refresh_frame_flags: slot 0 holds LAST
-        for (int i = 0; i < 7; i++) w.put(0, 3);   // ref_frame_idx[i] = 0
+        w.put((uint32_t)fp.refresh, 8); // refresh_frame_flags: the buffer that holds LAST from now on
+        for (int i = 0; i < 7; i++)     // ref_frame_idx[i]: LAST2 names the cached picture, the rest LAST's buffer
+            w.put((uint32_t)(i == 1 ? fp.last2_buf : fp.last_buf), 3);
         w.put(0, 1);                    // render_and_frame_size_different
         w.put(0, 1);                    // allow_high_precision_mv
         w.put(0, 1);                    // is_filter_switchable
@@ -193,13 +194,7 @@ void write_frame_header(BitWriter& w, const Av1Geo& g, const FrameParams& fp) {
 CpuAv1Encoder::CpuAv1Encoder(const h264::EncoderConfig& cfg, int tcl, int trl) : fe(front_config(cfg)) {
     const int W = fe.g.W, H = fe.g.H;
     // tiles: as many as the level allows (the entropy coder's parallel axis), 16x16 SB max per tile side
-    const int sbc = (W + 63) / 64, sbr = (H + 63) / 64;
-    int want_c = tcl, want_r = trl;
-    int auto_c, auto_r;
-    auto_tiles(sbc, sbr, &auto_c, &auto_r);
-    if (want_c < 0) want_c = auto_c;
-    if (want_r < 0) want_r = auto_r;
-    geo_init(geo, W, H, want_c, want_r);
+    session_geo(geo, W, H, tcl, trl);
     blk.assign((size_t)geo.c8 * geo.r8, BlkInfo{});
     lev.assign((size_t)fe.g.mb_w * fe.g.mb_h * kLevPerUnit, 0);
     lctx_w[0] = geo.mi_cols;
@@ -446,16 +441,19 @@ void CpuAv1Encoder::decide_key() {
         }
 }
 
-// One motion-compensated block: prediction from fe.ref, residual, reconstruction.
+// One motion-compensated block: prediction from its slice's reference (the previous picture,
+// or the cached one its tile row matched: ltr.h), residual, reconstruction.
 void CpuAv1Encoder::inter_block(int r, int c, int bsl, int mv_row, int mv_col) {
     const h264::Geometry& g = fe.g;
     const int log2n = bsl + 2, n = 1 << log2n, x = c * 4, y = r * 4;
     uint8_t py[256], pu[64], pv[64];
-    mc_block(fe.ref[0].data(), g.stride_y, geo.W - 1, geo.H - 1, x, y, n, n, 0, mv_row, mv_col, py, n);
+    const int slice = (r >> 2) / fe.g.rows_per_slice;
+    const std::vector<uint8_t>* ref = fe.ref0(slice);
+    mc_block(ref[0].data(), g.stride_y, geo.W - 1, geo.H - 1, x, y, n, n, 0, mv_row, mv_col, py, n);
     const int cn = n >> 1, cx = x >> 1, cy = y >> 1;
     const int lxc = ((geo.W + 1) >> 1) - 1, lyc = ((geo.H + 1) >> 1) - 1;
-    mc_block(fe.ref[1].data(), g.stride_c, lxc, lyc, cx, cy, cn, cn, 1, mv_row, mv_col, pu, cn);
-    mc_block(fe.ref[2].data(), g.stride_c, lxc, lyc, cx, cy, cn, cn, 1, mv_row, mv_col, pv, cn);
+    mc_block(ref[1].data(), g.stride_c, lxc, lyc, cx, cy, cn, cn, 1, mv_row, mv_col, pu, cn);
+    mc_block(ref[2].data(), g.stride_c, lxc, lyc, cx, cy, cn, cn, 1, mv_row, mv_col, pv, cn);
     int16_t* lp[3] = {unit_lev(r, c, bsl, 0), unit_lev(r, c, bsl, 1), unit_lev(r, c, bsl, 2)};
     int16_t* ly = lp[0];
     int16_t* lu = lp[1];
@@ -494,6 +492,7 @@ void CpuAv1Encoder::inter_block(int r, int c, int bsl, int mv_row, int mv_col) {
     b.mv_row = (int16_t)mv_row;
     b.mv_col = (int16_t)mv_col;
     b.mode = GLOBALMV;
+    b.pad1 = (uint8_t)(ref != fe.ref);   // LAST2: the cached picture
     set_cells(r, c, bsl, b);
     const int n4 = 1 << bsl;
     set_lctx(0, c, r, n4, nz ? level_summary(ly, n * n) : 0);
@@ -643,6 +642,7 @@ std::vector<uint8_t> CpuAv1Encoder::assemble(const std::vector<std::vector<uint8
 void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, std::vector<h264::EncodedPacket>& out) {
     fe.load_frame(bgrx, stride);
     fe.ctl_.plan(fe.stripe_dirty.data(), fe.tasks.data());
+    if (fe.ltr_slots_) fe.ltr_plan();   // long-term cache (ltr.h, buffer map): one decision per tile row
     const int ns = fe.g.num_slices;
     bool key = false;
     for (int s = 0; s < ns; s++) {
@@ -661,6 +661,14 @@ void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, s
     fe.ctl_.rate_control(fe.tasks.data(), fe.me.data());   // K10
     fp.key = key;
     fp.screen = key && palette_on;
+    if (fe.ltr_slots_) {   // the buffers the header names, from the map before this frame's commit
+        const ltr::LtrState& ls = fe.ltr_state[ns];
+        int slot = -1;
+        for (int s = 0; s < ns; s++) slot = sk_max(slot, fe.ltr_task[s].slot);   // one slot per frame (ltr_av1_reduce)
+        fp.last_buf = ltr::ltr_av1_last_buf(ls);
+        fp.last2_buf = slot >= 0 ? ls.st_fn[slot] : fp.last_buf;
+        fp.refresh = 1 << ltr::ltr_av1_new_buf(fe.ltr_slots_, ls, fe.ltr_task[0].store_slot);
+    }
     uint8_t tab[52];
     for (int q = 0; q < 52; q++) tab[q] = (uint8_t)qidx_for_qp(q);
     std::vector<std::vector<uint8_t>> tiles(geo.tile_cols * geo.tile_rows);

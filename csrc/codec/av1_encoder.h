@@ -30,6 +30,10 @@ struct FrameParams {
     int tile_size_bytes = 4;
     int lf_level = 0;     // loop_filter_level[0..3] (one level, av1_lf.h lf_level_for)
     int screen = 0;       // allow_screen_content_tools: palette blocks (key frames)
+    // Reference buffers of an inter frame (long-term cache, ltr.h buffer map; off: buffer 0 throughout)
+    int refresh = 0x01;   // refresh_frame_flags: the buffer the picture is written to
+    int last_buf = 0;     // ref_frame_idx[0] and [2..6]: the previous picture (LAST)
+    int last2_buf = 0;    // ref_frame_idx[1]: the cached picture the frame reads (LAST2), else last_buf
 };
 
 // Palette coding of key frames (av1_core.h): on unless SK_AV1_PALETTE=0 (A/B runs).

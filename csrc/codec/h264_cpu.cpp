@@ -37,7 +37,8 @@ CpuH264Encoder::CpuH264Encoder(const EncoderConfig& c) : cfg(c) {
     fs_mv.assign((size_t)g.num_mbs() * 2, 0);
     tasks.assign(g.num_slices, SliceTask());
     ltr_slots_ = ltr_slots_of(cfg);
-    ltr_excl_ = ltr_slots_ > 0 && cfg.codec == 1;
+    ltr_excl_ = ltr_slots_ > 0 && cfg.codec >= 1;
+    ltr_unit_ = ltr_unit_slices_of(cfg);
     ltr_max_age_ = ltr_max_age_env();
     if (ltr_slots_) {
         for (int j = 0; j < ltr_slots_; j++)
@@ -374,6 +375,7 @@ void CpuH264Encoder::decide_scenecut(int s) {
             ref1 += me[mby * g.mb_w + mbx].ref == 1;
         }
     if (t.allow_scenecut && inter > intra) t.final_action = ACT_I;
+    if (ltr_unit_) return;   // AV1: set with the decision (ltr_av1_reduce), clean slices of a matched tile row included
     if (ltr_excl_) ltr_task[s].ref1_mbs = ltr::ltr_exclusive_mbs(ltr_task[s], t.final_action == ACT_P, t.num_rows * g.mb_w);
     else if (ltr_slots_) ltr_task[s].ref1_mbs = t.final_action == ACT_P ? ref1 : 0;   // the stream's cur_slot (ltr_commit)
 }
@@ -394,10 +396,12 @@ void CpuH264Encoder::ltr_plan() {
             key |= tasks[s].action == ACT_I;
         }
         planned_p = planned_p && !key;
-        if (ltr_excl_) ltr::ltr_expire(ltr_slots_, st, tasks[s0].frame_num, ltr_max_age_);
-        if (planned_p && ltr::ltr_large(nd, n) && st.valid)
+        if (ltr_excl_ && !ltr_unit_) ltr::ltr_expire(ltr_slots_, st, tasks[s0].frame_num, ltr_max_age_);
+        // AV1 (ltr_unit_): the unit is the tile row, so every slice is compared, clean ones too
+        auto compared = [&](int s) { return ltr_unit_ ? planned_p : tasks[s].action == ACT_P; };
+        if (planned_p && ltr::ltr_large(nd, n) && st.valid) {
             for (int s = s0; s < s1; s++) {
-                if (tasks[s].action != ACT_P) continue;
+                if (!compared(s)) continue;
                 const size_t o0 = (size_t)tasks[s].first_row * 16 * g.stride_y;
                 const size_t cnt = (size_t)tasks[s].num_rows * 16 * g.stride_y;
                 for (int c = 0; c < 1 + ltr_slots_; c++) {
@@ -409,8 +413,12 @@ void CpuH264Encoder::ltr_plan() {
                     ltr_sad[(size_t)s * ltr::kLtrSadCols + c] = sum;
                 }
             }
-        ltr::ltr_decide(ltr_slots_, st, nd, n, planned_p, tasks[s0].frame_num, kFrameNumMask, s0, s1,
-                        [&](int s) { return tasks[s].action == ACT_P; }, ltr_sad.data(), ltr_task.data());
+            if (ltr_unit_) ltr::ltr_sum_units(ltr_slots_, st.valid, s0, s1, ltr_unit_, ltr_sad.data());
+        }
+        ltr::ltr_decide(ltr_slots_, st, nd, n, planned_p, tasks[s0].frame_num, kFrameNumMask, s0, s1, compared,
+                        ltr_sad.data(), ltr_task.data());
+        if (ltr_unit_)
+            ltr::ltr_av1_reduce(ltr_slots_, s0, s1, [&](int s) { return tasks[s].num_rows * g.mb_w; }, ltr_task.data());
         for (int s = s0; s < s1; s++)
             if (ltr_task[s].slot >= 0 && !ltr_excl_) tasks[s].num_refs = 2;   // [previous picture, the slot]
     };
@@ -892,7 +900,10 @@ void CpuH264Encoder::finish_frame() {
     for (int p = 0; p < 3; p++) prev[p].swap(src[p]);
     if (ltr_slots_) {
         const int ns = g.num_slices;
-        if (ltr_excl_) {
+        if (ltr_unit_) {
+            ltr::ltr_commit_av1(ltr_slots_, ltr_state[ns], ctl_.picture_is_idr(tasks.data()), g.num_mbs(), 0, ns,
+                                ltr_task.data());
+        } else if (ltr_excl_) {
             ltr::ltr_commit_rps(ltr_slots_, ltr_state[ns], ctl_.picture_is_idr(tasks.data()), tasks[0].frame_num,
                                 g.num_mbs(), 0, ns, ltr_task.data());
         } else if (cfg.fullframe) {

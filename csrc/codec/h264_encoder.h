@@ -19,6 +19,7 @@
 #include "ratecontrol.h"
 #include "ltr.h"
 #include "hevc_level.h"
+#include "av1_geo.h"
 
 namespace sk {
 namespace h264 {
@@ -59,13 +60,20 @@ struct EncoderConfig {
     int subpel = 1;              // quarter-pel refinement of P vectors (K4c, H.264 and HEVC); AV1 keeps integer vectors
     int intra4x4 = 0;            // H.264 I slices may code MBs as I_NxN (nine 4x4 modes) where cheaper; off
                                  // by default like x264's ultrafast preset (partitions none)
-    int ltr_slots = 0;           // H.264 / HEVC long-term reference cache (ltr.h): pictures kept per stream for content
-                                 // that comes back (window switches); 0 = off, 1..8; excludes num_refs > 1
+    int ltr_slots = 0;           // long-term reference cache (ltr.h): pictures kept per stream for content that comes
+                                 // back (window switches); 0 = off, 1..8 (AV1: 1..7); H.264: excludes num_refs > 1
 };
 
-// Long-term cache slots in force: H.264 and HEVC (AV1 shares this configuration and the front end).
+// Long-term cache slots in force (the three codecs share this configuration and the front end).
 inline int ltr_slots_of(const EncoderConfig& c) {
-    return (c.codec == 0 || c.codec == 1) && c.ltr_slots > 0 ? (c.ltr_slots < ltr::kLtrMaxSlots ? c.ltr_slots : ltr::kLtrMaxSlots) : 0;
+    const int cap = c.codec == 2 ? ltr::kLtrAv1MaxSlots : ltr::kLtrMaxSlots;
+    return c.ltr_slots > 0 ? (c.ltr_slots < cap ? c.ltr_slots : cap) : 0;
+}
+
+// AV1: front-end slices in one tile row, the cache's decision unit (0: the slice is the unit).
+inline int ltr_unit_slices_of(const EncoderConfig& c) {
+    if (c.codec != 2 || ltr_slots_of(c) == 0) return 0;
+    return av1::tile_row_units(c.width, c.height, c.tile_cols_log2, c.tile_rows_log2) / (c.stripe_height / 16);
 }
 
 // HEVC cache expiry age in pictures (ltr.h ltr_expire): SK_HEVC_LTR_MAX_AGE=<n>, clipped to
@@ -77,7 +85,17 @@ inline int ltr_max_age_env() {
 
 // Why a configuration cannot run the long-term cache (nullptr: it can, or the cache is off).
 inline const char* ltr_config_error(const EncoderConfig& c) {
-    if ((c.codec != 0 && c.codec != 1) || c.ltr_slots <= 0) return nullptr;
+    if (c.ltr_slots <= 0) return nullptr;
+    if (c.codec == 2) {   // AV1: a decoder owns eight buffers, one of them holds the previous picture
+        if (c.ltr_slots > ltr::kLtrAv1MaxSlots)
+            return "ltr_slots must be 0 (off) or 1..7 for AV1: the decoder's eight reference buffers hold the "
+                   "previous picture and the cached ones";
+        if (c.stripe_height <= 0 ||
+            (av1::tile_row_units(c.width, c.height, c.tile_cols_log2, c.tile_rows_log2) * 16) % c.stripe_height)
+            return "ltr_slots: the AV1 tile height must be a multiple of stripe_height (a tile row predicts from "
+                   "one picture)";
+        return nullptr;
+    }
     if (c.ltr_slots > ltr::kLtrMaxSlots) return "ltr_slots must be 0 (off) or 1..8";
     if (c.codec == 1) {   // HEVC: current picture + previous picture + slots within some level's MaxDpbSize (A.4.2)
         if (hevc::level_idc_for((c.width + 15) & ~15, (c.height + 15) & ~15, c.fps, 2 + c.ltr_slots) < 0)

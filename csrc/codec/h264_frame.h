@@ -104,7 +104,8 @@ class CpuH264Encoder {
     // Long-term reference cache (cfg.ltr_slots, ltr.h): plane sets (a stripe's slot j lives at the stripe's
     // rows of set j), the per-stream state ([num_slices] stripes, then the picture's) and the per-slice decisions
     int ltr_slots_ = 0;
-    bool ltr_excl_ = false;   // HEVC: a matched slice predicts from its slot alone (ltr.h exclusive mode)
+    bool ltr_excl_ = false;   // HEVC, AV1: a matched slice predicts from its slot alone (ltr.h exclusive mode)
+    int ltr_unit_ = 0;        // AV1: slices per tile row, the decision unit (ltr.h buffer map); 0: the slice
     int ltr_max_age_ = ltr::kLtrMaxAge;   // exclusive mode: expiry age in pictures (SK_HEVC_LTR_MAX_AGE)
     // reference index 0 of slice s: its slot's planes in exclusive mode when it matched, else the previous picture
     const std::vector<uint8_t>* ref0(int s) const {

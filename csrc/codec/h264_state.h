@@ -6,8 +6,8 @@
 //   picture's, whose frame_num is also the next HEVC POC) | RcState (K10) | ref Y U V |
 //   ref1 Y U V (second reference) | last source Y U V (damage baseline) | mvfield int16[2 * num_mbs]
 // The reference planes are what the next frame predicts from (HEVC: after deblocking + SAO,
-// AV1: after loop filter + CDEF). That is version 3. With the H.264 long-term cache on
-// (ltr_slots > 0) the blob is version 4: the version-3 layout, then
+// AV1: after loop filter + CDEF). That is version 3. With the long-term cache on
+// (ltr_slots > 0; AV1: LtrState holds the buffer map) the blob is version 4: the version-3 layout, then
 //   LtrState[num_slices + 1] (last = the picture's, full-frame mode) | slot 0 Y U V | slot 1 Y U V | ...
 // state_sections() below is this list as code; sizes and all four walkers (CPU and HIP, export
 // and import) come from it.

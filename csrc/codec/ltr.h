@@ -240,5 +240,101 @@ SK_HD void ltr_commit_rps(int slots, LtrState& st, bool idr, int poc, int mbs, i
     st.n_st = 1;
 }
 
+// ---- exclusive mode with a buffer map (AV1) -------------------------------------------
+// An AV1 decoder owns eight reference buffers and a frame header names the ones it reads
+// and writes, so a cached picture is a buffer that later frames leave alone. A picture
+// cannot be moved after it was decoded: storing the previous picture into slot k means
+// that its buffer becomes slot k's and the new picture goes elsewhere. The decision unit is
+// a tile row (a run of `unit_slices` front-end slices) and a frame reads one slot at most.
+// The free fields hold the map: st_fn[j] = buffer of slot j (j < slots <= 7),
+// st_fn[kLtrMaxSlots] = buffer of the previous picture, n_st = 1 once one exists.
+constexpr int kLtrAv1MaxSlots = 7;   // eight buffers: the previous picture and the slots
+
+SK_HD int ltr_av1_last_buf(const LtrState& st) { return st.st_fn[kLtrMaxSlots]; }
+
+// Buffer the picture being coded is written to (refresh_frame_flags = 1 << it), from the
+// state before its commit: the previous picture's own buffer without a store; with one, the
+// lowest buffer that neither the previous picture nor a slot other than store_slot holds
+// (store_slot's old buffer is free again).
+SK_HD int ltr_av1_new_buf(int slots, const LtrState& st, int store_slot) {
+    const int last = ltr_av1_last_buf(st);
+    if (store_slot < 0) return last;
+    int used = 1 << last;
+    for (int j = 0; j < slots; j++)
+        if (j != store_slot && ((st.valid >> j) & 1)) used |= 1 << st.st_fn[j];
+    int b = 0;
+    while ((used >> b) & 1) b++;   // 1 + slots <= 8 buffers are in use, so one below 8 is free
+    return b;
+}
+
+// The SADs of the slices of one unit summed and written back to each of them, so that
+// ltr_match gives every slice of a tile row the same slot.
+SK_HD void ltr_sum_units(int slots, int valid, int s0, int s1, int unit_slices, uint32_t* sad) {
+    for (int u0 = s0; u0 < s1; u0 += unit_slices) {
+        const int u1 = u0 + unit_slices < s1 ? u0 + unit_slices : s1;
+        for (int c = 0; c <= slots; c++) {
+            if (c > 0 && !((valid >> (c - 1)) & 1)) continue;
+            uint32_t sum = 0;
+            for (int s = u0; s < u1; s++) sum += sad[(size_t)s * kLtrSadCols + c];
+            for (int s = u0; s < u1; s++) sad[(size_t)s * kLtrSadCols + c] = sum;
+        }
+    }
+}
+
+// The one slot a frame reads: the slot matched by the most units over the tile rows
+// (`unit_slices` slices each, `units(s)`: units of slice s), ties to the lowest index; the
+// rows that matched another slot fall back to the previous picture. Sets ref1_mbs of every
+// slice: all of its units where it keeps a slot. Returns the slot, -1: none.
+template <class Units>
+SK_HD int ltr_av1_reduce(int slots, int s0, int s1, Units units, LtrTask* lt) {
+    int best = -1, best_n = 0;
+    for (int j = 0; j < slots; j++) {
+        int n = 0;
+        for (int s = s0; s < s1; s++)
+            if (lt[s].slot == j) n += units(s);
+        if (n > best_n) {
+            best_n = n;
+            best = j;
+        }
+    }
+    for (int s = s0; s < s1; s++) {
+        if (lt[s].slot != best) lt[s].slot = -1;
+        lt[s].ref1_mbs = lt[s].slot >= 0 ? units(s) : 0;
+    }
+    return best;
+}
+
+// ltr_commit for a stream whose cache is the buffer map (`key`: a key frame, which refreshes
+// all eight buffers: the cache is empty and the picture is in buffer 0).
+SK_HD void ltr_commit_av1(int slots, LtrState& st, bool key, int mbs, int s0, int s1, const LtrTask* lt) {
+    if (key) {
+        const int q = st.quiet_run;
+        ltr_state_reset(st);
+        st.quiet_run = q;
+        st.n_st = 1;
+        return;
+    }
+    const LtrTask& f = lt[s0];
+    if (f.flags & LTR_GATED) {
+        st.cur_slot = -1;
+        for (int j = slots - 1; j >= 0; j--) {
+            int cnt = 0;
+            for (int s = s0; s < s1; s++)
+                if (lt[s].slot == j) cnt += lt[s].ref1_mbs;
+            if (2 * cnt >= mbs) st.cur_slot = j;
+        }
+        if (st.cur_slot >= 0 && st.cur_slot == f.store_slot) st.cur_slot = -1;   // the slot now holds the previous content
+    } else if (f.flags & LTR_DRIFT) {
+        st.cur_slot = -1;
+    }
+    if (f.store_slot >= 0) {
+        const int nb = ltr_av1_new_buf(slots, st, f.store_slot);
+        st.st_fn[f.store_slot] = ltr_av1_last_buf(st);   // the previous picture stays where it is
+        st.valid |= 1 << f.store_slot;
+        st.st_fn[kLtrMaxSlots] = nb;
+    }
+    st.n_st = 1;
+}
+
 }  // namespace ltr
 }  // namespace sk

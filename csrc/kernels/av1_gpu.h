@@ -35,8 +35,9 @@ struct Av1Args {
     int tile_tok_cap;
     int* tok_off;             // [units] offset of the unit's tokens in its tile's stream
     int* tile_ntok;           // [tiles]
-    int* frame;               // device: [0] key, [1] qidx
-    int* frame_host;          // host-mapped copy of frame[0..2]
+    int* frame;               // device: [0] key, [1] qidx, [2] loop filter level
+    int* frame_host;          // host-mapped copy of frame[0..2]; with the long-term cache (ltr.h) the reference buffers
+                              // of the header: [3] refresh_frame_flags, [4] LAST's buffer, [5] LAST2's buffer
     h264::gpu::Planes cdef_in;   // the deblocked picture CDEF reads (k_av1_cdef writes f.rec)
     const uint8_t* qidx_of_qp;   // [52]
     int tile_cap;             // byte capacity per tile

@@ -466,6 +466,17 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
         A.frame_host[0] = key;
         A.frame_host[1] = qidx;
         A.frame_host[2] = lvl;
+        // long-term cache (ltr.h buffer map): the buffers the frame header names, from the map
+        // before this frame's commit (k_plan of the next frame); off: the host keeps buffer 0
+        if (f.ltr_unit) {
+            const ltr::LtrState& ls = f.ltr_state[ns];
+            int slot = -1;
+            for (int s = 0; s < ns; s++) slot = sk_max(slot, f.ltr_task[s].slot);   // one slot per frame (ltr_av1_reduce)
+            const int last = ltr::ltr_av1_last_buf(ls);
+            A.frame_host[3] = 1 << ltr::ltr_av1_new_buf(f.ltr_slots, ls, f.ltr_task[0].store_slot);
+            A.frame_host[4] = last;
+            A.frame_host[5] = slot >= 0 ? ls.st_fn[slot] : last;
+        }
     }
 }
 
@@ -647,7 +658,9 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
     }
 }
 
-// Inter frames: one wave per unit, vector from the front end's motion search.
+// Inter frames: one wave per unit, vector from the front end's motion search. kLtr: the
+// long-term cache is on (ltr.h); off, the kernel is the one-reference kernel it was.
+template <bool kLtr>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_av1_inter(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[4];
@@ -662,7 +675,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     if (u >= f.mb_w * f.mb_h) return;
     BlkLds& L = Lw[w];
     const int ux = u % f.mb_w, uy = u / f.mb_w;
-    const SliceTask t = f.tasks[uy / f.rows_per_slice];
+    const int slice = uy / f.rows_per_slice;   // wave-uniform
+    const SliceTask t = f.tasks[slice];
+    // the previous picture, or the cached one the unit's tile row matched (LAST2, ltr.h)
+    const h264::gpu::Planes ref = kLtr ? h264::gpu::ref0_planes(f, slice) : f.ref;
+    const uint8_t ref_last2 = kLtr ? (uint8_t)(ref.y != f.ref.y) : 0;
     const h264::MeResult me = f.me[u];
     const bool moving = t.final_action == ACT_P;
     const int mv_row = moving ? 8 * me.mvy : 0, mv_col = moving ? 8 * me.mvx : 0;
@@ -680,9 +697,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         // prediction (mc_block: window in L.lv, horizontal pass in L.a; both free until
         // code_block_wave)
         uint8_t* win = reinterpret_cast<uint8_t*>(L.lv);
-        mc_block(f.ref.y, f.stride_y, g.W - 1, g.H - 1, x, y, n, mv_row, mv_col, 0, n <= 4, win, L.a, L.pred);
-        mc_block(f.ref.u, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 256);
-        mc_block(f.ref.v, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 320);
+        mc_block(ref.y, f.stride_y, g.W - 1, g.H - 1, x, y, n, mv_row, mv_col, 0, n <= 4, win, L.a, L.pred);
+        mc_block(ref.u, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 256);
+        mc_block(ref.v, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 320);
         wsync();
         const uint32_t s = code_block_wave(L, F, log2n, qidx, false, lev_ptr(A, r, c, bsl, 0),
                                            lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
@@ -694,6 +711,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         b.mv_row = (int16_t)mv_row;
         b.mv_col = (int16_t)mv_col;
         b.mode = GLOBALMV;
+        b.pad1 = ref_last2;
         set_cells(A, r, c, bsl, b);
         const int n4 = 1 << bsl;
         set_lctx(A, 0, c, r, n4, (uint8_t)(s & 0xff));
@@ -1762,7 +1780,8 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_modes, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_rec, dim3(tiles), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(k_av1_inter, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    if (a.f.ltr_excl) hipLaunchKernelGGL(k_av1_inter<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_av1_inter<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_merge, dim3(a.geo.sb_cols * a.geo.sb_rows), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_av1_modes, dim3((a.geo.c8 * a.geo.r8 + 255) / 256), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_tokens, dim3((n + 3) / 4), dim3(256), 0, s, a);

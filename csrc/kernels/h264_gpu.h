@@ -81,7 +81,7 @@ struct FrameArgs {
     // 2 * ((W+1)/2)); yuv_fmt 0: BGRx input through k_convert_damage
     const uint8_t* yuv;
     int yuv_fmt;
-    // Long-term reference cache (codec/ltr.h), ltr_slots > 0: H.264 and HEVC. Slot j's planes lie at
+    // Long-term reference cache (codec/ltr.h), ltr_slots > 0. Slot j's planes lie at
     // ltr.y + j * ltr_ny and ltr.u / ltr.v + j * ltr_nc (a stripe's slot at the stripe's rows).
     int ltr_slots;
     Planes ltr;
@@ -91,12 +91,13 @@ struct FrameArgs {
     uint32_t* ltr_part;         // [num_slices][kLtrSadCols][rows_per_slice] zero-vector SADs per MB row (k_ltr_match)
     uint32_t* ltr_sad;          // [num_slices][kLtrSadCols] their sums (k_ltr_decide)
     int* ltr_cnt;               // [num_slices][2] the slice's stream: dirty MBs, SADs computed (gated frame)
-    int ltr_excl;               // HEVC: a matched slice predicts from its slot alone (ltr.h exclusive mode)
+    int ltr_excl;               // HEVC, AV1: a matched slice predicts from its slot alone (ltr.h exclusive mode)
+    int ltr_unit;               // AV1: slices per tile row, the decision unit (ltr.h buffer map); 0: the slice
     int ltr_max_age;            // exclusive mode: expiry age in pictures (ltr_expire)
 };
 
 #if defined(__HIPCC__)
-// Reference index 0 of slice s: the previous picture, or in exclusive mode (HEVC, ltr.h) the
+// Reference index 0 of slice s: the previous picture, or in exclusive mode (HEVC and AV1, ltr.h) the
 // cached picture a matched slice predicts from. s must be wave-uniform: the slot index goes
 // through readfirstlane, so the three base pointers are scalars (no per-lane select, no
 // indexed Planes array, which would live in scratch).

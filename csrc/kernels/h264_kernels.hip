@@ -897,7 +897,9 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
             for (int s = tid; s < ns; s += 256) idr &= a.tasks[s].final_action == ACT_I && a.tasks[s].idr_on_intra;
             idr = __syncthreads_and(idr);
             if (tid == 0) commit_picture(pic, idr, a.plan_cfg.num_refs);
-            if (a.ltr_excl && tid == 0)   // HEVC: the cache follows the picture's RPS (ltr.h)
+            if (a.ltr_unit && tid == 0)   // AV1: the cache is the decoder's buffer map (ltr.h)
+                ltr::ltr_commit_av1(a.ltr_slots, a.ltr_state[ns], idr, a.mb_w * a.mb_h, 0, ns, a.ltr_task);
+            else if (a.ltr_excl && tid == 0)   // HEVC: the cache follows the picture's RPS (ltr.h)
                 ltr::ltr_commit_rps(a.ltr_slots, a.ltr_state[ns], idr, a.tasks[0].frame_num, a.mb_w * a.mb_h, 0, ns,
                                     a.ltr_task);
             else if (a.ltr_slots && tid == 0)   // long-term cache: current slot and the marking model (ltr.h)
@@ -983,7 +985,8 @@ __global__ __launch_bounds__(256) void k_ltr_match(FrameArgs a) {
         a.ltr_cnt[2 * s] = nd;
         a.ltr_cnt[2 * s + 1] = gate;
     }
-    if (!gate || t.action != ACT_P || band >= t.num_rows || (c > 0 && !((valid >> (c - 1)) & 1))) return;
+    // AV1 (ltr_unit): the tile row is the unit, so the slices the plan left clean are compared too
+    if (!gate || (t.action != ACT_P && !a.ltr_unit) || band >= t.num_rows || (c > 0 && !((valid >> (c - 1)) & 1))) return;
     const uint8_t* ref = c ? a.ltr.y + (size_t)(c - 1) * a.ltr_ny : a.ref.y;
     const size_t o = (size_t)(t.first_row + band) * 16 * a.stride_y;
     const uint4* q = reinterpret_cast<const uint4*>(a.src.y + o);
@@ -1013,7 +1016,7 @@ __global__ __launch_bounds__(256) void k_ltr_decide(FrameArgs a) {
         const int s = i / ltr::kLtrSadCols, c = i - s * ltr::kLtrSadCols;
         const int valid = a.ltr_state[a.fullframe ? ns : s].valid;
         uint32_t sum = 0;
-        if (a.ltr_cnt[2 * s + 1] && a.tasks[s].action == ACT_P && c <= a.ltr_slots && (c == 0 || ((valid >> (c - 1)) & 1)))
+        if (a.ltr_cnt[2 * s + 1] && (a.tasks[s].action == ACT_P || a.ltr_unit) && c <= a.ltr_slots && (c == 0 || ((valid >> (c - 1)) & 1)))
             for (int b = 0; b < a.tasks[s].num_rows; b++) sum += a.ltr_part[(size_t)i * a.rows_per_slice + b];
         a.ltr_sad[i] = sum;
     }
@@ -1028,10 +1031,16 @@ __global__ __launch_bounds__(256) void k_ltr_decide(FrameArgs a) {
             anyp |= a.tasks[s].action == ACT_P;
             rows += a.tasks[s].num_rows;
         }
-        if (a.ltr_excl) ltr::ltr_expire(a.ltr_slots, a.ltr_state[ns], a.tasks[s0].frame_num, a.ltr_max_age);
-        ltr::ltr_decide(a.ltr_slots, a.ltr_state[a.fullframe ? ns : k], a.ltr_cnt[2 * s0], rows * a.mb_w, anyp && !key,
+        if (a.ltr_excl && !a.ltr_unit) ltr::ltr_expire(a.ltr_slots, a.ltr_state[ns], a.tasks[s0].frame_num, a.ltr_max_age);
+        const bool planned_p = anyp && !key;
+        if (a.ltr_unit && a.ltr_cnt[2 * s0 + 1])   // AV1: one sum per tile row, so its slices match the same slot
+            ltr::ltr_sum_units(a.ltr_slots, a.ltr_state[ns].valid, s0, s1, a.ltr_unit, a.ltr_sad);
+        ltr::ltr_decide(a.ltr_slots, a.ltr_state[a.fullframe ? ns : k], a.ltr_cnt[2 * s0], rows * a.mb_w, planned_p,
                         a.tasks[s0].frame_num, kFrameNumMask, s0, s1,
-                        [&](int s) { return a.tasks[s].action == ACT_P; }, a.ltr_sad, a.ltr_task);
+                        [&](int s) { return a.ltr_unit ? planned_p : a.tasks[s].action == ACT_P; }, a.ltr_sad,
+                        a.ltr_task);
+        if (a.ltr_unit)   // one slot per frame; ref1_mbs of every slice, clean ones included
+            ltr::ltr_av1_reduce(a.ltr_slots, s0, s1, [&](int s) { return a.tasks[s].num_rows * a.mb_w; }, a.ltr_task);
         for (int s = s0; s < s1; s++)
             if (a.ltr_task[s].slot >= 0 && !a.ltr_excl) a.tasks[s].num_refs = 2;   // [previous picture, the slot]
     }
@@ -1073,7 +1082,9 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
         const long long ts = red[0][0] + red[0][1] + red[0][2] + red[0][3];
         const long long td = red[1][0] + red[1][1] + red[1][2] + red[1][3];
         t.final_action = (p && ts > td) ? ACT_I : t.action;
-        if (a.ltr_excl)
+        if (a.ltr_unit) {
+            // AV1: set with the decision (ltr_av1_reduce): clean slices of a matched tile row count too
+        } else if (a.ltr_excl)
             a.ltr_task[s].ref1_mbs = ltr::ltr_exclusive_mbs(a.ltr_task[s], planned_p && t.final_action == ACT_P, t.num_rows * a.mb_w);
         else if (a.ltr_slots)
             a.ltr_task[s].ref1_mbs = (planned_p && t.final_action == ACT_P) ? red1[0] + red1[1] + red1[2] + red1[3] : 0;

@@ -120,7 +120,6 @@ class CaptureSession {
                     e.fullframe = 1;
                     e.aq_strength = 0;
                     e.intra4x4 = 0;
-                    if (e.codec == 2) e.ltr_slots = 0;   // the long-term cache is H.264 / HEVC only
                     e.deblock = 0;   // their own in-loop filters, not the H.264 front end's
                 }
                 if (const char* err = h264::ltr_config_error(e)) throw std::runtime_error(err);

@@ -537,7 +537,9 @@ class HipBackend : public EncoderBackend {
         copy_now(lt.data(), args_.ltr_task, sizeof(ltr::LtrTask) * ns);
         const std::vector<SliceTask>& tasks = pc.tasks;
         if (!pc.commit) return ls;
-        if (args_.ltr_excl)
+        if (args_.ltr_unit)
+            ltr::ltr_commit_av1(slots, ls[ns], pc.idr, g_.num_mbs(), 0, ns, lt.data());
+        else if (args_.ltr_excl)
             ltr::ltr_commit_rps(slots, ls[ns], pc.idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
         else if (cfg_.fullframe)
             ltr::ltr_commit(slots, ls[ns], true, pc.idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
@@ -654,7 +656,8 @@ class HipBackend : public EncoderBackend {
         a.ref1 = make_planes();
         a.rec = make_planes();
         a.ltr_slots = ltr_slots_of(cfg_);
-        a.ltr_excl = a.ltr_slots > 0 && cfg_.codec == 1;   // HEVC: one reference per slice (ltr.h exclusive mode)
+        a.ltr_excl = a.ltr_slots > 0 && cfg_.codec >= 1;   // HEVC, AV1: one reference per slice (ltr.h exclusive mode)
+        a.ltr_unit = ltr_unit_slices_of(cfg_);             // AV1: the tile row decides (ltr.h buffer map)
         a.ltr_max_age = ltr_max_age_env();
         if (a.ltr_slots) {   // long-term cache (codec/ltr.h): slot plane sets, stream states, per-frame decisions
             const size_t ny = (size_t)g_.stride_y * g_.plane_h_y, nc = (size_t)g_.stride_c * g_.plane_h_c;
@@ -951,12 +954,7 @@ class HipBackend : public EncoderBackend {
         const int n = g_.num_mbs();
         av1::gpu::Av1Args& a = aargs_;
         memset(&a, 0, sizeof(a));
-        const int sbc = (g_.W + 63) / 64, sbr = (g_.H + 63) / 64;
-        int ac, ar;
-        av1::auto_tiles(sbc, sbr, &ac, &ar);
-        const int tc = cfg_.tile_cols_log2 >= 0 ? cfg_.tile_cols_log2 : ac;
-        const int tr = cfg_.tile_rows_log2 >= 0 ? cfg_.tile_rows_log2 : ar;
-        av1::geo_init(av1_geo_, g_.W, g_.H, tc, tr);
+        av1::session_geo(av1_geo_, g_.W, g_.H, cfg_.tile_cols_log2, cfg_.tile_rows_log2);
         a.geo = av1_geo_;
         a.blk = mem_.dmalloc<av1::BlkInfo>((size_t)av1_geo_.c8 * av1_geo_.r8);
         a.pal = mem_.dmalloc<uint8_t>((size_t)av1_geo_.c8 * av1_geo_.r8 * 8);
@@ -1002,7 +1000,7 @@ class HipBackend : public EncoderBackend {
         for (auto& f : slot_) {
             f.av1_out = mem_.mapped<uint8_t>((size_t)a.out_cap);
             f.av1_size = mem_.mapped<int>(tiles, hipHostMallocCoherent);
-            f.av1_frame = mem_.mapped<int>(4, hipHostMallocCoherent);
+            f.av1_frame = mem_.mapped<int>(8, hipHostMallocCoherent);
         }
         HIPCHECK(hipStreamSynchronize(stream_));
         av1_level_ = av1::choose_level_idx(g_.W, g_.H, cfg_.fps);
@@ -1014,6 +1012,11 @@ class HipBackend : public EncoderBackend {
         fp.key = f.av1_frame.host[0];
         fp.qidx = f.av1_frame.host[1];
         fp.lf_level = f.av1_frame.host[2];
+        if (args_.ltr_unit) {   // long-term cache: the reference buffers k_av1_setup chose (ltr.h buffer map)
+            fp.refresh = f.av1_frame.host[3];
+            fp.last_buf = f.av1_frame.host[4];
+            fp.last2_buf = f.av1_frame.host[5];
+        }
         fp.screen = fp.key && aargs_.palette;
         std::vector<std::vector<uint8_t>> tl(tiles);
         size_t off = 0;

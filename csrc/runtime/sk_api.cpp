@@ -54,7 +54,7 @@ template <class V>
 DebugBuf bytes_of(const V& v) { return {v.data(), (int64_t)(v.size() * sizeof(*v.data()))}; }
 
 // The debug_buffer names of each codec's own buffers; the front end's are resolved by CpuBackend.
-// The long-term cache's buffers live in the front end (H.264 and HEVC).
+// The long-term cache's buffers live in the front end.
 DebugBuf ltr_debug(h264::CpuH264Encoder& e, const std::string& s) {
     if (s == "ltr_state") return bytes_of(e.ltr_state);
     if (s == "ltr_task") return bytes_of(e.ltr_task);
@@ -86,6 +86,7 @@ DebugBuf codec_debug(av1::CpuAv1Encoder& e, const std::string& s) {
     if (s == "levels") return bytes_of(e.lev);
     if (s == "av1_geo") return {&e.geo, (int64_t)sizeof(av1::Av1Geo)};
     if (s == "av1_qidx") return {&e.fp.qidx, 4};
+    if (s.compare(0, 3, "ltr") == 0) return ltr_debug(e.fe, s);
     return {nullptr, -1};
 }
 
@@ -233,7 +234,6 @@ h264::EncoderConfig to_config(const sk_h264_config* c) {
         e.fullframe = 1;
         e.num_refs = 1;
         e.deblock = 0;
-        if (e.codec == 2) e.ltr_slots = 0;   // the long-term cache is H.264 / HEVC only
     }
     return e;
 }

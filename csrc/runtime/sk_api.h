@@ -29,8 +29,8 @@ typedef struct sk_h264_config {
     int32_t tile_rows_log2;
     int32_t rc_mode;                // K10 rate control: 0 = constant QP, 1 = CRF (qp = CRF), 2 = CBR
     int32_t bitrate_kbps;           // CBR target (VBV = 1.5 frame intervals)
-    int32_t ltr_slots;              // H.264 / HEVC long-term reference cache: pictures kept per stream, 0 = off,
-                                    // 1..8; H.264: refused together with num_refs > 1
+    int32_t ltr_slots;              // long-term reference cache: pictures kept per stream, 0 = off, 1..8 (AV1: 1..7);
+                                    // H.264: refused together with num_refs > 1
 } sk_h264_config;
 
 typedef struct sk_packet {
@@ -171,7 +171,7 @@ typedef struct sk_capture_settings {
     // < 0: no exhaustive +-16 search candidate, diamond search only (x264 "ultrafast"-like
     // CPU plumbing; with h264_subpel < 0 the CPU encoder runs 640x480 at ~55 fps on one core)
     int32_t h264_me_full;
-    int32_t h264_ltr_slots;    // long-term reference cache slots per stream (H.264 and HEVC sessions): 0 = off, 1..8
+    int32_t h264_ltr_slots;    // long-term reference cache slots per stream: 0 = off, 1..8 (AV1 sessions: 1..7)
 } sk_capture_settings;
 
 typedef struct sk_stripe_result {

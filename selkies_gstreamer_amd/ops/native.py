@@ -341,8 +341,8 @@ class H264Encoder:
                  aq_strength: float = 0.0, subpel: bool = True, intra4x4: bool = False,
                  tile_cols_log2: int = -1, tile_rows_log2: int = -1, rate_control: str = "cqp",
                  bitrate_kbps: int = 0, ltr_slots: int = 0):
-        """ltr_slots: long-term reference cache (H.264 and HEVC), pictures kept per stream (stripe, or
-        the picture in full-frame mode) for content that comes back, 0 = off, 1..8; H.264: not with
+        """ltr_slots: long-term reference cache, pictures kept per stream (stripe, or the picture in
+        full-frame mode) for content that comes back, 0 = off, 1..8 (AV1: 1..7); H.264: not with
         num_refs > 1. aq_strength: MB-level adaptive QP (h264_mb.h aq_offset), 1.0 = x264 aq-mode 1
         strength; 0 = constant QP per slice (x264 ultrafast behaviour). deblock: True / False,
         or "auto" (the slices coded at QP >= 34, h264_encoder.h slice_deblock)."""
@@ -611,7 +611,17 @@ class Av1Encoder(H264Encoder):
     """AV1 Main (8-bit 4:2:0) encoder session: full-frame pictures coded as OBU
     temporal units (temporal delimiter, sequence header on key frames, one OBU_FRAME
     with all tiles), same front end as the H.264 encoder. Packets carry the 10-byte
-    stripe header + the temporal unit (low-overhead bitstream format)."""
+    stripe header + the temporal unit (low-overhead bitstream format).
+
+    ltr_slots = 1..7 keeps that many settled pictures as long-term references (csrc/codec/ltr.h). A
+    cached picture is one of the decoder's eight reference buffers that later frame headers leave
+    alone (`refresh_frame_flags`); storing the previous picture sends the new one to another
+    buffer. When a window comes back, every block of a tile row that matches the cached picture
+    predicts from it as LAST2 (`ref_frame_idx[1]`), with the full motion search; a frame reads one
+    cached picture at most, and the tile rows that match none predict from the previous picture.
+    The tile height must be a multiple of stripe_height (the default 64 always is); 8 slots, or a
+    stripe_height that does not divide the tile height, is refused. With ltr_slots = 0 every byte
+    is what it was without the option."""
 
     def __init__(self, width: int, height: int, **kw):
         kw.pop("fullframe", None)

@@ -183,10 +183,12 @@ class Capture:
 
 
 def _ltr_slots_from_env(name: str = "SELKIES_H264_LTR_SLOTS") -> int:
-    """SELKIES_H264_LTR_SLOTS / SELKIES_HEVC_LTR_SLOTS: long-term reference pictures cached per H.264
-    stream / per HEVC (x265enc) session (0 = off, at most 8). Each variable means its own codec only."""
+    """SELKIES_H264_LTR_SLOTS / SELKIES_HEVC_LTR_SLOTS / SELKIES_AV1_LTR_SLOTS: long-term reference
+    pictures cached per H.264 stream / per HEVC (x265enc) session / per AV1 (svtav1enc) session (0 =
+    off, at most 8; AV1 at most 7: the decoder's eight buffers hold the previous picture too). Each
+    variable means its own codec only."""
     try:
-        return max(0, min(8, int(os.environ.get(name, "0") or 0)))
+        return max(0, min(7 if "AV1" in name else 8, int(os.environ.get(name, "0") or 0)))
     except ValueError:
         return 0
 
@@ -883,10 +885,11 @@ class DataStreamingServer:
             cs.h264_aq_strength = max(0, min(64, int(self.settings.h264_aq_strength)))
             cs.h264_subpel = 0 if self.settings.h264_subpel[0] else -1
             cs.h264_intra4x4 = int(bool(self.settings.h264_intra4x4[0]))
-            # long-term reference cache (csrc/codec/ltr.h), 0 = off: H.264 and HEVC, each from its own variable
+            # long-term reference cache (csrc/codec/ltr.h), 0 = off: each codec from its own variable
             # (h264_ltr_slots is the front end's field, like h264_crf)
             cs.h264_ltr_slots = (_ltr_slots_from_env() if cs.output_mode == 1 else
-                                 _ltr_slots_from_env("SELKIES_HEVC_LTR_SLOTS") if cs.output_mode == 2 else 0)
+                                 _ltr_slots_from_env("SELKIES_HEVC_LTR_SLOTS") if cs.output_mode == 2 else
+                                 _ltr_slots_from_env("SELKIES_AV1_LTR_SLOTS") if cs.output_mode == 3 else 0)
         cs.use_paint_over_quality = int(bool(p["use_paint_over_quality"]))
         cs.paint_over_trigger_frames, cs.damage_block_threshold, cs.damage_block_duration = 15, 10, 20
         cs.use_cpu = int(bool(p["use_cpu"]))

@@ -1,5 +1,5 @@
 """Window switches with and without the long-term reference cache (EncoderConfig::ltr_slots), H.264
-(the default) or HEVC (--codec hevc: one full-frame session per setting).
+(the default), HEVC or AV1 (--codec hevc / av1: one full-frame session per setting).
 
 One 1080p session per mode (striped, full frame) and per setting (ltr_slots 0 and 4) on the
 same build, fed the same sequence: two full-screen desktops A and B that alternate, each
@@ -8,7 +8,7 @@ and setting: bytes and host-side encode time of the switch-back frames (the firs
 content the session has shown before) and the steady-state frame time (the quiet frames between
 switches), with the two settings alternating frame by frame so both see the same machine state.
 
-    python tools/ltr_switch.py [--backend hip|cpu] [--cycles N] [--slots K] [--codec h264|hevc]
+    python tools/ltr_switch.py [--backend hip|cpu] [--cycles N] [--slots K] [--codec h264|hevc|av1]
 
 Run under `rocprofv3 --kernel-trace --stats -- python tools/ltr_switch.py --only-ltr` for the
 k_ltr_match / k_ltr_decide / k_commit times (tools/rocprof_summary.py reads the result).
@@ -21,7 +21,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from selkies_gstreamer_amd.ops.native import H264Encoder, HevcEncoder  # noqa: E402
+from selkies_gstreamer_amd.ops.native import Av1Encoder, H264Encoder, HevcEncoder  # noqa: E402
 from selkies_gstreamer_amd.utils.synthetic import SyntheticDesktop  # noqa: E402
 
 
@@ -33,7 +33,7 @@ def main():
     ap.add_argument("--slots", type=int, default=4)
     ap.add_argument("--settle", type=int, default=12, help="frames each content is shown before a switch")
     ap.add_argument("--cycles", type=int, default=6, help="A/B switch pairs after both contents were cached")
-    ap.add_argument("--codec", default="h264", choices=["h264", "hevc"])
+    ap.add_argument("--codec", default="h264", choices=["h264", "hevc", "av1"])
     ap.add_argument("--only-ltr", action="store_true", help="run only the sessions with the cache (kernel traces)")
     a = ap.parse_args()
     W, H = a.width, a.height
@@ -52,12 +52,14 @@ def main():
         return f
 
     def make(mode, s):
+        if a.codec == "av1":
+            return Av1Encoder(W, H, stripe_height=64, backend=a.backend, use_paint_over=False, ltr_slots=s)
         if a.codec == "hevc":
             return HevcEncoder(W, H, stripe_height=64, backend=a.backend, use_paint_over=False, ltr_slots=s)
         return H264Encoder(W, H, stripe_height=64, fullframe=mode == "fullframe", backend=a.backend,
                            use_paint_over=False, ltr_slots=s)
 
-    for mode in (("hevc",) if a.codec == "hevc" else ("striped", "fullframe")):
+    for mode in ((a.codec,) if a.codec != "h264" else ("striped", "fullframe")):
         settings = [a.slots] if a.only_ltr else [0, a.slots]
         encs = {s: make(mode, s) for s in settings}
         stats = {s: {"sw_bytes": [], "sw_ms": [], "steady_ms": [], "key": 0} for s in settings}
