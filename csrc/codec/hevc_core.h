@@ -115,8 +115,69 @@ constexpr int kCoefPerCu = 384;     // per unit: 16x16 luma | 8x8 Cb | 8x8 Cr, r
                                     // across the slots of its units z0..z3 (kT32Cb / kT32Cr offsets)
 constexpr int kCoefCb = 256, kCoefCr = 320;
 constexpr int kT32Cb = 1024, kT32Cr = 1280, kT32Coefs = 1536;
-constexpr int kCuBinCap = 4096;     // bin entries per CU slot (worst case ~3950, see bin_bound)
+constexpr int kCuBinCap = 4096;     // bin entries per CU slot (worst case bin_bound::kUnit = 2868, below)
 constexpr int kSubstreamCtbBytes = 4608;   // worst-case CABAC bytes per CTB (>= 6 bits x ctx bins)
+
+// The most entries (BinBuf: one per context or terminating bin, one per 8 bins of a bypass run)
+// that binarize_slice / k_hevc_bins can put into one unit's slot, over every level quant_level can
+// return. A unit always holds 384 coefficients = 24 sub-blocks, whatever its transform tree.
+namespace bin_bound {
+constexpr int kLevelClamp = 32767;   // = kMaxLevel (asserted there)
+constexpr int kScaleQp0 = 26214;     // = quant_scale(0), the largest scale
+constexpr int kRoundIntra = 240;     // = kQuantRoundIntra (asserted there), the larger rounding offset
+// The largest |level| of an n x n TU, n = 1 << log2n: |coefficient| <= 2^15 (fwd_transform of 8-bit
+// residuals: each stage at most 255 * 64 * n >> its shift = 32640; ts_forward: 255 * 32), QP 0, the
+// intra rounding offset.
+constexpr int max_level(int log2n) {
+    const int qbits = 14 + 7 - log2n;
+    const long long l = ((1ll << 15) * kScaleQp0 + ((long long)kRoundIntra << (qbits - 9))) >> qbits;
+    return l < kLevelClamp ? (int)l : kLevelClamp;
+}
+// Entries of one coeff_abs_level_remaining of value rem at Rice parameter rice (code_sb): not
+// decreasing in rem.
+constexpr int rem_entries(int rem, int rice) {
+    if (rem < (3 << rice)) return 1 + (rice ? 1 : 0);   // prefix <= 4 bins, suffix rice <= 4 bins
+    int v = rem - (3 << rice), len = rice;
+    while (v >= (1 << len)) {
+        v -= 1 << len;
+        len++;
+    }
+    const int ones = 3 + len + 1 - rice;   // escape prefix in runs of 16 bins, then len suffix bins
+    return 2 * (ones / 16) + (ones % 16 + 7) / 8 + (len + 7) / 8;
+}
+constexpr int rem_entries_max(int level) {   // over the Rice parameters 0..4, base level 1
+    int m = 0;
+    for (int rice = 0; rice <= 4; rice++) m = rem_entries(level - 1, rice) > m ? rem_entries(level - 1, rice) : m;
+    return m;
+}
+constexpr int sub_block(int log2n) {   // code_sb of a sub-block with 16 levels
+    return 1                                           // coded_sub_block_flag
+           + 16                                        // sig_coeff_flag
+           + 8                                         // coeff_abs_level_greater1_flag
+           + 1                                         // coeff_abs_level_greater2_flag
+           + 2                                         // 16 sign bins
+           + 16 * rem_entries_max(max_level(log2n));   // coeff_abs_level_remaining
+}
+constexpr int prologue(int log2n) {   // code_last
+    return (log2n == 2 ? 1 : 0)        // transform_skip_flag
+           + 2 * (2 * log2n - 1)       // last_sig_coeff_x/y_prefix
+           + (log2n > 2 ? 2 : 0);      // the two suffixes, <= 3 bins each
+}
+constexpr int max4(int a, int b, int c, int d) { return (a > b ? a : b) > (c > d ? c : d) ? (a > b ? a : b) : (c > d ? c : d); }
+constexpr int kSao = 2 + 2 * 2 + 3 * (4 + 4 + 1);   // sao_bins: merge flags, two type indices, per plane 4 offsets, 4 signs, band / class
+constexpr int kPu = 1 + 2 + 2 + 2 * (4 + 1) + 1;    // code_pu: merge_flag, mvd greater0/1, two EG1 remainders (<= 32 bins) + signs, mvp flag
+constexpr int kTree16 = 3 + 4 * (1 + 2 + 4);        // code_tt16 flags: split, 2 chroma cbfs; per node split, 2 chroma cbfs, 4 luma cbfs
+constexpr int kIntraCu8s = 4 * (1 + 4 + 4 + 1 + 1 + 2 + 4);   // per CU8: part_mode, 4 prev_intra flags, 4 mpm / rem modes, chroma mode, code_tt8 flags
+constexpr int kInterCu32 = 1 + 1 + 2 + 2 * kPu + 1 + 1 + 2 + kTree16;   // skip, pred_mode, part_mode, two PUs, rqt_root_cbf, split, 2 chroma cbfs, the node
+constexpr int kUnit = kSao                                                        // the CTB's SAO syntax (its first unit)
+                      + 2                                                         // split_cu_flag of the CTB and of the CU16
+                      + (kIntraCu8s > kInterCu32 ? kIntraCu8s : kInterCu32)       // CU headers and tree flags
+                      + 24 * prologue(2)                                          // 24 4x4 TUs: the most prologues
+                      + 24 * max4(sub_block(2), sub_block(3), sub_block(4), sub_block(5))   // the 384 levels
+                      + 2;                                                        // end_of_slice_segment_flag, end_of_subset_one_bit
+static_assert(kUnit == 2868, "bin_bound changed: update the comment on kCuBinCap");
+static_assert(kUnit <= kCuBinCap, "a unit's bins can overflow its slot (BinBuf does not check)");
+}   // namespace bin_bound
 
 // ---------------------------------------------------------------------------
 // Per-unit decisions (40 bytes, shared by CPU and GPU buffers; tests diff them).
@@ -561,11 +622,13 @@ SK_HD void ts_inverse(const int* d, int* res) {
 SK_HD int quant_scale(int r) { return r == 0 ? 26214 : r == 1 ? 23302 : r == 2 ? 20560 : r == 3 ? 18396 : r == 4 ? 16384 : 14564; }
 SK_HD int level_scale(int r) { return r == 0 ? 40 : r == 1 ? 45 : r == 2 ? 51 : r == 3 ? 57 : r == 4 ? 64 : 72; }
 constexpr int kMaxLevel = 32767;
+static_assert(kMaxLevel == bin_bound::kLevelClamp, "bin_bound derives the slot size from this clamp");
 // Rounding offsets of the quantiser (Q9: 240 / 512 = 0.47 intra, 150 / 512 = 0.29 inter).
 // The RD zeroing of whole TUs (J = SSE + lambda R) removes what does not pay, so the levels
 // themselves round nearer than HM's 1/3 and 1/6 dead zones: -1.8 % (desktop) / -1.2 %
 // (motion) BD-rate at 640x360 (tools/rd_codecs.py, CPU, 8 frames per point).
 constexpr int kQuantRoundIntra = 240, kQuantRoundInter = 150;
+static_assert(kQuantRoundIntra == bin_bound::kRoundIntra && kQuantRoundInter <= kQuantRoundIntra, "bin_bound::max_level");
 SK_HD int quant_level(int c, int qp, int log2n, bool intra) {
     const int qbits = 14 + qp / 6 + (7 - log2n);
     const int64_t add = (int64_t)(intra ? kQuantRoundIntra : kQuantRoundInter) << (qbits - 9);

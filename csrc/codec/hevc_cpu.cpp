@@ -798,6 +798,9 @@ void CpuHevcEncoder::binarize_slice(int s) {
                 // end_of_slice_segment_flag: the last CTB of the slice (a split row: of its segment)
                 const bool end = m.split(r) ? c + 1 == m.x1(r, m.seg(c, r)) : r == r1 - 1 && c == geo.ctb_w - 1;
                 w.term(end);
+                // end_of_subset_one_bit closes the substream of every row of the slice but its last; it
+                // lives in the slot of the row's last unit, as in k_hevc_bins (bin_n counts it there too)
+                if (!m.split(r) && r != r1 - 1 && c == geo.ctb_w - 1) w.term(1);
             }
             bin_n[idx] = w.n;
         }
@@ -806,8 +809,8 @@ void CpuHevcEncoder::binarize_slice(int s) {
 
 // One slice segment NAL: CTB rows cy0 .. cy0 + rows - 1, CTB columns [x0, x1) of each (a
 // split row: one row, one segment), one CABAC substream per row - its units' bin chunks in
-// coding order - with WPP storage after the second CTB, entry points for the rows after
-// the first.
+// coding order, end_of_subset_one_bit included - with WPP storage after the second CTB, entry
+// points for the rows after the first.
 std::vector<uint8_t> CpuHevcEncoder::write_segment(const SliceTask& t, int cy0, int rows, int x0, int x1, bool idr) {
     const bool p_slice = t.final_action != ACT_I;
     const UnitGrid ug = geo.grid();
@@ -829,7 +832,6 @@ std::vector<uint8_t> CpuHevcEncoder::write_segment(const SliceTask& t, int cy0, 
                 const uint16_t* b = &bins[(size_t)u * kCuBinCap];
                 cu[j - j0].assign(b, b + bin_n[u]);
             }
-            if (r + 1 < rows) cu.back().push_back((uint16_t)((1u << 8) | CTX_TERM));   // end_of_subset_one_bit
             std::vector<uint32_t> dt, dr, dtl;
             sub[r] = pc_code_row_host(cu, ctx, &dt, &dr, &dtl);
             if (pc_dbg_.size() != (size_t)3 * geo.units()) pc_dbg_.assign((size_t)3 * geo.units(), 0);
@@ -861,7 +863,6 @@ std::vector<uint8_t> CpuHevcEncoder::write_segment(const SliceTask& t, int cy0, 
             for (int i = 0; i < bin_n[u]; i++) e.code_entry(b[i], ctx);
             if (j + 1 == jsync_end) memcpy(sync, ctx, CTX_COUNT);   // WPP storage after the second CTB
         }
-        if (r + 1 < rows) e.terminate(1);   // end_of_subset_one_bit
         e.finish();
         sub[r].resize(e.pos);
         payload_bytes_ += (long long)e.pos;

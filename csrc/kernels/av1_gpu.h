@@ -13,8 +13,47 @@ namespace av1 {
 namespace gpu {
 
 constexpr int kLevPerUnit = 384;
-constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case ~3.3k, see tok_bound)
+constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2707, below)
 constexpr int kTileChunkCap = 1 << 20;
+
+// The most tokens code_unit (av1_core.h; k_av1_tokens) can put into one unit's slot, over every
+// level quantize can return. A unit with residual is one 16x16 block (luma 16x16 + two 8x8 chroma
+// transform blocks) or four 8x8 blocks (luma 8x8 + two 4x4 each); larger blocks carry no residual.
+// Literal bits are packed 24 to a token; a symbol first flushes the pending bits as a token of their own.
+namespace tok_bound {
+constexpr int kLevelCap = 4095;      // quantize: |level| <= 4095
+constexpr int golomb_bits(int a) {   // code_coeffs: Golomb code of a - 14 (a > 14)
+    int len = 0;
+    while (((a - 14) >> (len + 1)) != 0) len++;
+    return 2 * len + 1;
+}
+constexpr int kCoefs = 256 + 2 * 64;                        // levels of a unit
+constexpr int kCoefBits = 1 + golomb_bits(kLevelCap);       // sign + Golomb remainder: 24
+constexpr int kTxbs = 4 * 3;                                // transform blocks of four 8x8 blocks
+constexpr int kTxbHead = 1 + 1 + 1 + 1 + 1 + 1 + 1;         // txb_skip, tx set, eob_pt, eob_extra, its literal bits, dc_sign, the
+                                                            // bits left over after the block's full 24-bit literals
+constexpr int kPaletteBits = 16 + 8 + 2 + 7 * 8;            // cache flags, first colour, extra bits, seven deltas
+constexpr int kKeyHead = 1 + 1 + 1 + 1 + 1                  // skip, y mode, angle delta, uv mode, angle delta
+                         + 1 + 1                            // palette_y_mode, palette_y_size
+                         + (kPaletteBits + 23) / 24 + 1     // the colours' literals (the first may join pending bits)
+                         + 1;                               // palette_uv_mode
+constexpr int kMvComp = 1 + 1 + 10 + 1;                     // sign, class, class bits, fraction
+constexpr int kInterHead = 1 + 1 + 3                        // skip, is_inter, three single_ref symbols
+                           + 1 + 2                          // new_mv, two drl symbols (zero_mv / ref_mv: without a vector)
+                           + 1 + 2 * kMvComp;               // mv_joint, both components
+constexpr int kPaletteMap = 64 - 1 + 1 + 1;                 // an 8x8 block: the other 63 indices, the first as literal bits, its flush
+constexpr int kPartition = 2 + 1 + 4;                       // the 64 and 32 nodes the unit opens, its own, four 8x8 nodes
+constexpr int kBlocks = 4;
+constexpr int kHead = kKeyHead + kPaletteMap > kInterHead ? kKeyHead + kPaletteMap : kInterHead;
+constexpr int kUnit = kPartition                            // partition symbols
+                      + kBlocks * kHead                     // mode info (and index maps) of four blocks
+                      + kTxbs * kTxbHead                    // per transform block
+                      + kCoefs * (1 + 4)                    // coeff_base(_eob) + four coeff_br per level
+                      + kCoefs * kCoefBits / 24;            // full literals of the sign / Golomb runs
+static_assert(kCoefBits == 24 && 256 * kCoefBits <= 256 * 32, "a 16x16 block's sign / Golomb run fits the 256-word LDS bit buffer");
+static_assert(kUnit == 2707, "tok_bound changed: update the comment on kTokCap");
+static_assert(kUnit <= kTokCap, "a unit's tokens can overflow its slot (the tokens past it are dropped)");
+}   // namespace tok_bound
 
 struct Av1Args {
     h264::gpu::FrameArgs f;   // planes, geometry (mb = 16x16 unit), tasks, motion field

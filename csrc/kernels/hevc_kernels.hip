@@ -1444,7 +1444,8 @@ __global__ __launch_bounds__(192) void k_hevc_sync(HevcArgs A) {
         const int prev = r0 + rr - 1;
         if (A.cw >= 2) {
             const uint16_t* co = A.coff + ((size_t)prev * kPcCtxOff + c) * RC;
-            const int jn = ug.ctb_chunk0(prev, 2);
+            // the first two CTBs' chunks; a row of two CTBs with a one-unit last CTB has 6, not 8
+            const int jn = A.cw > 2 ? ug.ctb_chunk0(prev, 2) : ug.row_chunks(prev);
             for (int j = 0; j < jn; j++) {
                 const uint16_t* sp = A.srt + (size_t)ug.chunk_unit(prev, j) * kCuBinCap;
                 const int hi = co[RC + j];

@@ -594,6 +594,7 @@ class HipBackend : public EncoderBackend {
             {"tokc", 2, v.tokc, tiles * v.tile_tok_cap * 4},
             {"tile_ntok", 2, v.tile_ntok, tiles * 4},
             {"frame", 2, v.frame, 16},   // key, qidx, lf level, -
+            {"av1_qidx", 2, v.frame ? v.frame + 1 : nullptr, 4},   // the CPU back end's name for frame[1]
             {"tile_size", 2, v.tile_size, tiles * 4},
             {"coefs", 1, h.coefs, nmb * hevc::kCoefPerCu * 2},
             {"cus", 1, h.cus, (int64_t)(nmb * sizeof(hevc::CuInfo))},
