@@ -15,7 +15,9 @@
 //   k_motion_search   K4     the candidate + diamond search alone (me_full off)
 //   k_decide                 per-slice scene-cut decision
 //   k_rc_qp           K10    frame QP: one lane's serial chain, on LDS copies of its inputs
-//   k_code_inter      K6     MC, transform, quant/decimation, QP escalation, recon
+//   k_code_inter      K6+K5  P slices: MC, transform, quant/decimation, QP escalation, recon (an MB
+//                            whose levels are all zero, or decimated away, skips what follows the
+//                            quantiser); I slices: the open-loop pre-pass (modes + start QP)
 //   k_code_intra      K5+K6  Intra16x16 wavefront (one wave per MB row, lag 2); where I slices are
 //                            sub-sliced (mb_w > kIntraSubMbs) k_code_intra_sub is launched instead
 //   k_cavlc           K8     per-MB CAVLC: lanes code residual blocks in parallel,
@@ -200,6 +202,7 @@ __device__ __forceinline__ void stamp(unsigned long long* dbg, int step, int poi
 #define STAMP(step, pt)
 #define STAMP_S(dbg, step, pt)
 #endif
+constexpr int kCodeStampRow = 62;   // stamp row of k_code_inter (k_me keeps row 63)
 
 // Big-endian-in-word bit writer on a shared/global u32 buffer (atomicOr, so
 // several lanes may write disjoint bit ranges concurrently).
@@ -1287,14 +1290,21 @@ __device__ __forceinline__ int quad_sum(int v) {
     return v;
 }
 
+// What quant_analyse leaves for quant_bound, per lane.
+struct QuantState {
+    int cbp_l, cbp_c;
+    int bn_l, bc_l, lastl;   // this quad's luma block: TotalCoeff, bound bits of the levels, last scan position
+    int bn_c, bc_c, lastc;   // its chroma AC block (lanes < 32)
+    int dc_nz, dc_crude;     // Intra16x16 luma DC level of lanes 0..15
+    int cdc_nz, cdc_crude;   // chroma DC level of lanes 0..7
+};
+
 // Per-lane quantisation of this lane's luma row and chroma row into LDS, then the
 // same analysis as quant_luma / quant_chroma of the CPU path. Returns cbp and
-// writes per-block TotalCoeff into S.nnz. The MB size check first uses a
-// lane-parallel conservative bound and only runs the exact (nC-free) CAVLC bound
-// of mb_bits_bound when that one exceeds the budget: same decisions as the CPU.
-__device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int qp, bool intra16, MbScratch& S,
-                              int* bound_out, const CavlcTables& T, int* sl, int* sc,
-                              unsigned long long* dbg = nullptr, int step = 0) {
+// writes per-block TotalCoeff into S.nnz. Needs no CAVLC table: k_code_inter runs it
+// before it knows whether its workgroup loads them.
+__device__ __forceinline__ int quant_analyse(const int* wl, const int* wc, int qp, bool intra16, MbScratch& S,
+                              int* sl, int* sc, QuantState& Q, unsigned long long* dbg = nullptr, int step = 0) {
     const int l = lane_id();
     const int b = l >> 2, r = l & 3;
     const int cl = l & 31, comp = cl >> 4, cb = (cl >> 2) & 3;
@@ -1303,6 +1313,11 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
     int ln_c = 0, lc_c = 0;   // chroma AC row
     int lvl[4], lvc[4];       // this lane's quantised levels (|.|) for the bound
     int lastl = -1, lastc = -1;  // highest scan position holding a non-zero level
+    // Inter MBs (wave-uniform, by ballot): every luma level / every chroma AC level is zero before
+    // decimation. Such a part has score 0, no coded block and no bound term: its LDS level writes,
+    // decimation walks, reductions and block bounds are skipped (the LDS region is cleared once,
+    // below, if the MB still stores levels), with the results the full analysis gives.
+    bool luma_zero = false, cac_zero = false;
     // ---- luma ----
     {
         int qbits = 15 + qp / 6;
@@ -1315,12 +1330,15 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
             int lv = quant_coef(wl[j], sel3(pos_class(pos), m0, m1, m2), f, qbits);
             if (intra16 && pos == 0) lv = 0;
             sl[j] = lv;   // kept in registers for the reconstruction
-            S.coef[kCoefLuma + b * 16 + ((izz_row >> (8 * j)) & 255)] = (int16_t)lv;
             lvl[j] = sk_abs(lv);
             ln_l += lv != 0;
             if (lv) lastl = sk_max(lastl, (int)((izz_row >> (8 * j)) & 255));
         }
-
+        luma_zero = !intra16 && __ballot(ln_l != 0) == 0ull;
+        if (!luma_zero) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) S.coef[kCoefLuma + b * 16 + ((izz_row >> (8 * j)) & 255)] = (int16_t)sl[j];
+        }
         if (!intra16 && l < 16) S.coef[kCoefLumaDC + l] = 0;
     }
     // ---- chroma ----
@@ -1335,15 +1353,22 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
             int pos = r * 4 + j;
             int lv = pos == 0 ? 0 : quant_coef(wc[j], sel3(pos_class(pos), m0, m1, m2), f, qbits);
             sc[j] = lv;
-            if (l < 32) S.coef[kCoefChromaAC + (comp * 4 + cb) * 16 + ((izz_row >> (8 * j)) & 255)] = (int16_t)lv;
             lvc[j] = sk_abs(lv);
             ln_c += lv != 0;
             if (lv) lastc = sk_max(lastc, (int)((izz_row >> (8 * j)) & 255));
         }
+        cac_zero = !intra16 && __ballot(l < 32 && ln_c != 0) == 0ull;
+        if (!cac_zero && l < 32) {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                S.coef[kCoefChromaAC + (comp * 4 + cb) * 16 + ((izz_row >> (8 * j)) & 255)] = (int16_t)sc[j];
+        }
         if (l < 32 && r == 0) S.dcc[comp * 4 + cb] = wc[0];
     }
     STAMP_S(dbg, step, 9);
-    {
+    int bn_l = 0, bc_l = 0;   // per luma block
+    int bn_c = 0, bc_c = 0;   // per chroma block (lanes < 32)
+    if (!(luma_zero && cac_zero)) {
         int sl_l = suffix_len_cap(quad_max(sk_max(sk_max(lvl[0], lvl[1]), sk_max(lvl[2], lvl[3]))));
         int sl_c = suffix_len_cap(quad_max(sk_max(sk_max(lvc[0], lvc[1]), sk_max(lvc[2], lvc[3]))));
 #pragma unroll
@@ -1353,9 +1378,9 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
         }
         lastl = quad_max(lastl);
         lastc = quad_max(lastc);
+        bn_l = quad_sum(ln_l), bc_l = quad_sum(lc_l);
+        bn_c = quad_sum(ln_c), bc_c = quad_sum(lc_c);
     }
-    int bn_l = quad_sum(ln_l), bc_l = quad_sum(lc_l);   // per luma block
-    int bn_c = quad_sum(ln_c), bc_c = quad_sum(lc_c);   // per chroma block (lanes < 32)
     wave_sync();
     // I16 luma DC: Hadamard + quant (lanes 0..15 = raster positions)
     int dc_crude = 0, dc_nz = 0;
@@ -1388,10 +1413,10 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
     wave_sync();
     STAMP_S(dbg, step, 10);
     // ---- cbp analysis ----
-    int cbp_l;
+    int cbp_l = 0;
     if (intra16) {
         cbp_l = __ballot(bn_l > 0) ? 15 : 0;
-    } else {
+    } else if (!luma_zero) {
         // decimation scores (sequential per block, lanes 0..15)
         int score = l < 16 ? decimate_score(S.coef + kCoefLuma + l * 16, 16) : 0;
         int s4 = score + __shfl_down(score, 1) + __shfl_down(score, 2) + __shfl_down(score, 3);
@@ -1406,8 +1431,8 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
         if (mb_score < 6) cbp_l = 0;
     }
     // chroma: per component decimation (inter), cbp chroma; block b of lanes 4b..4b+3
-    int comp_ac[2], chroma_score[2];
-    {
+    int comp_ac[2] = {0, 0}, chroma_score[2] = {0, 0};
+    if (!cac_zero) {
         int cscore = 0;
         if (!intra16 && l < 8) cscore = decimate_score(S.coef + kCoefChromaAC + l * 16 + 1, 15);
 #pragma unroll
@@ -1424,10 +1449,26 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
     }
     bool any_dc = __ballot(cdc_nz != 0) != 0ull;
     int cbp_c = (comp_ac[0] || comp_ac[1]) ? 2 : (any_dc ? 1 : 0);
+#ifdef SK_STAMPS   // point 13: 1 = all levels zero before decimation, 2 = decimated to cbp 0, 3 = coded
+    if (dbg && blockIdx.x == SK_STAMP_BLOCK && threadIdx.x == 0 && (unsigned)(step - SK_STAMP_STEP0) < 64u)
+        dbg[(step - SK_STAMP_STEP0) * 16 + 13] =
+            (cbp_l | cbp_c) ? 3 : ((__ballot(ln_l != 0 || (l < 32 && ln_c != 0)) | (any_dc ? 1ull : 0ull)) ? 2 : 1);
+#endif
+    if (!intra16 && cbp_l == 0 && cbp_c == 0) {
+        // Nothing is coded: the bound is mb_bits_bound's constant part (96), reconstruction is the
+        // prediction, nnz[] and the stored levels are zero (the caller writes them from registers).
+        return 0;
+    }
+    if (luma_zero) {   // levels are stored from LDS: 256 luma levels, two words per lane
+        uint32_t* c32 = reinterpret_cast<uint32_t*>(S.coef + kCoefLuma);
+        c32[2 * l] = 0;
+        c32[2 * l + 1] = 0;
+    }
+    if (cac_zero) reinterpret_cast<uint32_t*>(S.coef + kCoefChromaAC)[l] = 0;   // 128 chroma AC levels
     // zero decimated blocks (LDS) and their counts
     bool luma_coded = intra16 ? (cbp_l != 0) : ((cbp_l >> (b >> 2)) & 1);
     if (!intra16 && !luma_coded) {
-        if (r == 0) {
+        if (r == 0 && !luma_zero) {
             for (int k = 0; k < 16; k++) S.coef[kCoefLuma + b * 16 + k] = 0;
         }
         bn_l = 0;
@@ -1447,6 +1488,21 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
     if (r == 0) S.nnz[b] = luma_coded ? (uint8_t)bn_l : 0;
     if (l < 32 && r == 0) S.nnz[16 + comp * 4 + cb] = cbp_c == 2 ? (uint8_t)bn_c : 0;
     STAMP_S(dbg, step, 11);
+    Q = QuantState{cbp_l, cbp_c, bn_l, bc_l, lastl, bn_c, bc_c, lastc, dc_nz, dc_crude, cdc_nz, cdc_crude};
+    return cbp_l | (cbp_c << 4);
+}
+
+// The MB size check of an analysed MB (cbp != 0, or Intra16x16): first a lane-parallel
+// conservative bound, and the exact (nC-free) CAVLC bound of mb_bits_bound only when that
+// one exceeds the budget: same decisions as the CPU.
+__device__ __forceinline__ int quant_bound(const QuantState& Q, bool intra16, const MbScratch& S, const CavlcTables& T,
+                                           unsigned long long* dbg = nullptr, int step = 0) {
+    const int l = lane_id();
+    const int b = l >> 2, r = l & 3;
+    const int cbp_l = Q.cbp_l, cbp_c = Q.cbp_c;
+    const int bn_l = Q.bn_l, bc_l = Q.bc_l, lastl = Q.lastl, bn_c = Q.bn_c, bc_c = Q.bc_c, lastc = Q.lastc;
+    const int dc_nz = Q.dc_nz, dc_crude = Q.dc_crude, cdc_nz = Q.cdc_nz, cdc_crude = Q.cdc_crude;
+    const bool luma_coded = intra16 ? (cbp_l != 0) : ((cbp_l >> (b >> 2)) & 1);
     // ---- size check: conservative bound first ----
     // block bound: longest coeff_token for n, exact total_zeros code, run_before
     // <= 2/3 bits per coefficient while zerosLeft <= 2/6 (+8 beyond), level bounds
@@ -1476,10 +1532,7 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
     STAMP_S(dbg, step, 12);
     if (dbg && blockIdx.x == SK_STAMP_BLOCK && threadIdx.x == 0 && (unsigned)(step - SK_STAMP_STEP0) < 64u)
         dbg[(step - SK_STAMP_STEP0) * 16 + 14] = total_crude;
-    if (total_crude <= kMbBitBudget || intra16) {   // Intra16x16: the conservative bound decides
-        *bound_out = total_crude;
-        return cbp_l | (cbp_c << 4);
-    }
+    if (total_crude <= kMbBitBudget || intra16) return total_crude;   // Intra16x16: the conservative bound decides
     // ---- exact bound (same terms as mb_bits_bound) ----
     int bnd = 0;
     if (l < 16) {
@@ -1496,8 +1549,17 @@ __device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int 
             bnd = bc.n;
         }
     }
-    *bound_out = 96 + wave_sum(bnd);
-    return cbp_l | (cbp_c << 4);
+    return 96 + wave_sum(bnd);
+}
+
+// quant_analyse and the size bound of its result (an inter MB with cbp 0 has the constant 96).
+__device__ __forceinline__ int quant_mb_lanes(const int* wl, const int* wc, int qp, bool intra16, MbScratch& S,
+                              int* bound_out, const CavlcTables& T, int* sl, int* sc,
+                              unsigned long long* dbg = nullptr, int step = 0) {
+    QuantState Q;
+    const int cbp = quant_analyse(wl, wc, qp, intra16, S, sl, sc, Q, dbg, step);
+    *bound_out = (!intra16 && cbp == 0) ? 96 : quant_bound(Q, intra16, S, T, dbg, step);
+    return cbp;
 }
 
 // Reconstruct this lane's luma row (4 px) and chroma row (lanes < 32).
@@ -1977,56 +2039,53 @@ __global__ __launch_bounds__(256) void k_subpel(FrameArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// K6 inter: one wave per MB of a P slice (SKIPALL slices just record skips).
-// 4 waves per workgroup, one MB per wave: the CAVLC tables are loaded once per 4 MBs.
-__global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
-    if (a.gate && *a.gate == 0) return;   // CBR second pass not needed
-    __shared__ MbScratch Sw[4];
-    __shared__ QpelLds Qw[4];   // fractional-MV luma MC
-    __shared__ CavlcTables T;
-    MbScratch& S = Sw[threadIdx.x >> 6];
-    int nmb = a.mb_w * a.mb_h;
-    int idx = xcd_remap(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);
-    const bool valid = idx < nmb;
-    int mbx = valid ? idx % a.mb_w : 0, mby = valid ? idx / a.mb_w : 0;
-    int s = mby / a.rows_per_slice;
-    const SliceTask t = a.tasks[s];
-    int l = lane_id();
-    if (valid && t.final_action == ACT_SKIPALL && l == 0) {
-        MbInfo z;
-        memset(&z, 0, sizeof(z));
-        a.mbs[idx] = z;
-        a.me[idx].mvx = 0;
-        a.me[idx].mvy = 0;
-        a.me[idx].ref = 0;
-        a.me[idx].fx = a.me[idx].fy = 0;
-    }
-    // Blocks with no P macroblock (skipped / intra / out-of-range) leave before the table load.
-    const bool coded = valid && t.final_action == ACT_P;
-    if (!__syncthreads_or(coded)) return;
-    load_cavlc_tables(T, a.cavlc_tabs);
-    __syncthreads();
-    if (!coded) return;
+// K6 inter, the work of one wave on MB idx of P slice s (task t), in two halves: everything up to
+// the cbp at the start QP needs no CAVLC table, the size bound of a coded MB and what follows do.
+struct InterMb {   // per lane, from code_inter_begin to code_inter_finish
+    int mvx, mvy, refi, pmx, pmy, smx, smy;
+    int pred_l[4], pred_c[4];   // prediction of this lane's luma / chroma row
+    int wl[4], wc[4];           // its transformed residual
+    int sl[4], sc[4];           // its levels at qp
+    int qp, cbp;
+    QuantState q;
+};
+#ifdef SK_STAMPS   // points of row kCodeStampRow: tools/stamps_code.py
+#define CODE_STAMP_DBG(a) ((a).dbg)
+#else
+#define CODE_STAMP_DBG(a) nullptr
+#endif
+
+// Q: the wave's interpolation window. Returns the cbp at the start QP.
+__device__ __forceinline__ int code_inter_begin(const FrameArgs& a, const SliceTask& t, int s, int idx, int mbx, int mby,
+                                                MbScratch& S, QpelLds& Q, InterMb& m) {
+    const int l = lane_id();
+    unsigned long long* const dbg = CODE_STAMP_DBG(a);
+    STAMP_S(dbg, kCodeStampRow, 0);
     // MV prediction from the final motion field (all MBs of a P slice are inter)
-    auto nbr = [&](int ox, int oy, bool ok) {
+    // The four neighbour entries and the MB's own: five independent loads from indices that are
+    // valid either way (an unavailable neighbour reads the MB's own entry and is masked after it).
+    // Loads under the availability tests are issued one by one, each behind the wait for the last.
+    const bool top = mby > t.first_row;
+    const bool okA = mbx > 0, okB = top, okC = top && mbx + 1 < a.mb_w, okD = top && mbx > 0;
+    const MeResult eA = a.me[okA ? idx - 1 : idx], eB = a.me[okB ? idx - a.mb_w : idx];
+    const MeResult eC = a.me[okC ? idx - a.mb_w + 1 : idx], eD = a.me[okD ? idx - a.mb_w - 1 : idx];
+    const MeResult eO = a.me[idx];
+    auto nbr = [](const MeResult& e, bool ok) {
         MvNb n;
         n.avail = ok;
-        n.ref = ok ? a.me[oy * a.mb_w + ox].ref : -1;
-        n.mvx = ok ? me_qx(a.me[oy * a.mb_w + ox]) : 0;
-        n.mvy = ok ? me_qy(a.me[oy * a.mb_w + ox]) : 0;
+        n.ref = ok ? e.ref : -1;
+        n.mvx = ok ? me_qx(e) : 0;
+        n.mvy = ok ? me_qy(e) : 0;
         return n;
     };
-    bool top = mby > t.first_row;
-    MvNb A = nbr(mbx - 1, mby, mbx > 0);
-    MvNb B = nbr(mbx, mby - 1, top);
-    MvNb C = nbr(mbx + 1, mby - 1, top && mbx + 1 < a.mb_w);
-    if (!C.avail) C = nbr(mbx - 1, mby - 1, top && mbx > 0);
-    const int refi = a.me[idx].ref;
+    const MvNb A = nbr(eA, okA), B = nbr(eB, okB), C = okC ? nbr(eC, true) : nbr(eD, okD);
+    const int refi = eO.ref;
     const Planes rp = refi ? ref1_planes(a, s) : a.ref;
     int pmx, pmy, smx, smy;
     mv_pred16x16(A, B, C, refi, &pmx, &pmy);
     mv_pskip(A, B, C, &smx, &smy);
-    int mvx = me_qx(a.me[idx]), mvy = me_qy(a.me[idx]);
+    int mvx = me_qx(eO), mvy = me_qy(eO);
+    STAMP_S(dbg, kCodeStampRow, 1);
 
     const int b = l >> 2, r = l & 3;
     const int cl = l & 31, comp = cl >> 4, cb = (cl >> 2) & 3;
@@ -2041,7 +2100,6 @@ __global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; j++) pred_l[j] = (pw >> (8 * j)) & 255;
     } else {   // fractional: interpolation window through LDS (k_subpel's QpelLds)
-        QpelLds& Q = *reinterpret_cast<QpelLds*>(&Qw[threadIdx.x >> 6]);
         qpel_fill(Q, rp.y, a.stride_y, a.stride_y, ylo, yhi, mbx * 16 + (mvx >> 2) - 3, mby * 16 + (mvy >> 2) - 3);
 #pragma unroll
         for (int j = 0; j < 4; j++)
@@ -2062,13 +2120,69 @@ __global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
         pred_c[j] = chroma_mc_sample(cbase, a.stride_c, a.stride_c, t.pic_rows * 8, cx0 + j,
                                      cy0 - t.pic_row0 * 8, mvx, mvy);
     }
+    STAMP_S(dbg, kCodeStampRow, 2);
+    int x[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) x[j] = src_l[j] - pred_l[j];
+    fwd4_quad(x, r, m.wl);
+#pragma unroll
+    for (int j = 0; j < 4; j++) x[j] = src_c[j] - pred_c[j];
+    fwd4_quad(x, r, m.wc);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        m.pred_l[j] = pred_l[j];
+        m.pred_c[j] = pred_c[j];
+    }
+    STAMP_S(dbg, kCodeStampRow, 3);
+    // wave-uniform: table lookups become scalar loads
+    m.qp = __builtin_amdgcn_readfirstlane(a.aq_strength > 0 ? aq_start_qp(t.qp, a.aq[idx]) : t.qp);
+    m.cbp = quant_analyse(m.wl, m.wc, m.qp, false, S, m.sl, m.sc, m.q, dbg, kCodeStampRow);
+    m.mvx = mvx, m.mvy = mvy, m.refi = refi;
+    m.pmx = pmx, m.pmy = pmy, m.smx = smx, m.smy = smy;
+    return m.cbp;
+}
+
+// QP escalation on the size bound, reconstruction, levels and MbInfo.
+__device__ __forceinline__ void code_inter_finish(const FrameArgs& a, const SliceTask& t, int idx, int mbx, int mby,
+                                                  MbScratch& S, const CavlcTables& T, InterMb& m) {
+    const int l = lane_id();
+    const int b = l >> 2, r = l & 3;
+    const int cl = l & 31, comp = cl >> 4, cb = (cl >> 2) & 3;
+    const int px = mbx * 16 + blk_x(b) * 4, py = mby * 16 + blk_y(b) * 4 + r;
+    const int cx0 = mbx * 8 + (cb & 1) * 4, cy0 = mby * 8 + (cb >> 1) * 4 + r;
+    unsigned long long* const dbg = CODE_STAMP_DBG(a);
+    const int cap = sk_min(51, t.qp + 24);
+    int qp = m.qp, cbp = m.cbp;
+    for (;;) {   // code_mb's loop; cbp 0: the bound is mb_bits_bound's constant part, no table is read
+        const int bound = cbp == 0 ? 96 : quant_bound(m.q, false, S, T, dbg, kCodeStampRow);
+        if (qp + 6 > cap || bound <= mb_bit_budget(false)) break;
+        qp += 6;
+        wave_sync();
+        cbp = quant_analyse(m.wl, m.wc, qp, false, S, m.sl, m.sc, m.q, dbg, kCodeStampRow);
+    }
+    STAMP_S(dbg, kCodeStampRow, 4);
     MbInfo mb;
     memset(&mb, 0, sizeof(mb));
     mb.type = MB_P_16x16;
+    mb.cbp = (uint8_t)cbp;
+    mb.qp = (uint8_t)qp;
     int rec_l[4], rec_c[4];
-    code_mb(src_l, pred_l, src_c, pred_c, t.qp, false, S, mb, rec_l, rec_c,
-            a.coefs + (size_t)idx * kCoefPerMb, T, nullptr, 0,
-            a.aq_strength > 0 ? aq_start_qp(t.qp, a.aq[idx]) : -1);
+    uint32_t* g32 = reinterpret_cast<uint32_t*>(a.coefs + (size_t)idx * kCoefPerMb);   // 816 B = 204 words
+    if (cbp == 0) {   // wave-uniform: rec = pred, every level is zero
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            rec_l[j] = m.pred_l[j];
+            rec_c[j] = m.pred_c[j];
+        }
+        for (int i = l; i < kCoefPerMb / 2; i += 64) g32[i] = 0;
+    } else {
+        recon_mb_lanes(qp, false, cbp, S, m.pred_l, m.pred_c, rec_l, rec_c, m.sl, m.sc);
+        STAMP_S(dbg, kCodeStampRow, 5);
+        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(S.coef);
+        for (int i = l; i < kCoefPerMb / 2; i += 64) g32[i] = s32[i];
+    }
+    STAMP_S(dbg, kCodeStampRow, 6);
+    const int mvx = m.mvx, mvy = m.mvy, refi = m.refi, pmx = m.pmx, pmy = m.pmy, smx = m.smx, smy = m.smy;
     // recon
     uint32_t rw = (uint32_t)rec_l[0] | ((uint32_t)rec_l[1] << 8) | ((uint32_t)rec_l[2] << 16) |
                   ((uint32_t)rec_l[3] << 24);
@@ -2079,6 +2193,7 @@ __global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
                       ((uint32_t)rec_c[3] << 24);
         *reinterpret_cast<uint32_t*>(cr + (size_t)cy0 * a.stride_c + cx0) = cw;
     }
+    STAMP_S(dbg, kCodeStampRow, 7);
     if (l == 0) {
         mb.mvx = (int16_t)mvx;
         mb.mvy = (int16_t)mvy;
@@ -2089,9 +2204,11 @@ __global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
             mb.mvdx = (int16_t)(mvx - pmx);
             mb.mvdy = (int16_t)(mvy - pmy);
         }
-        for (int i = 0; i < 24; i++) mb.nnz[i] = S.nnz[i];
+        if (mb.cbp)   // cbp == 0: every TotalCoeff is 0 (the memset above), S.nnz is not written
+            for (int i = 0; i < 24; i++) mb.nnz[i] = S.nnz[i];
         a.mbs[idx] = mb;
     }
+    STAMP_S(dbg, kCodeStampRow, 8);
 }
 
 // ---------------------------------------------------------------------------
@@ -2255,23 +2372,10 @@ __device__ void load_nb_planes(const Planes& P, int sy, int sc, int mbx, int mby
 // modes against the SOURCE neighbours and the QP the MB needs under the bit budget
 // with that prediction. k_code_intra's wavefront then only predicts, quantises from
 // that QP and reconstructs (no mode search, usually no escalation in the chain).
-__global__ __launch_bounds__(256) void k_intra_prep(FrameArgs a) {
-    if (a.gate && *a.gate == 0) return;   // CBR second pass not needed
-    __shared__ MbScratch Sw[4];
-    __shared__ CavlcTables T;
-    __shared__ uint8_t nb_w[4][64];   // top 16 | left 16 | ctop 2x8 | cleft 2x8
-    MbScratch& S = Sw[threadIdx.x >> 6];
-    uint8_t* nb = nb_w[threadIdx.x >> 6];
-    const int nmb = a.mb_w * a.mb_h;
-    const int idx = xcd_remap(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);
-    const bool valid = idx < nmb;
-    const int mbx = valid ? idx % a.mb_w : 0, mby = valid ? idx / a.mb_w : 0;
-    const SliceTask t = a.tasks[mby / a.rows_per_slice];
-    const bool coded = valid && t.final_action == ACT_I;
-    if (!__syncthreads_or(coded)) return;
-    load_cavlc_tables(T, a.cavlc_tabs);
-    __syncthreads();
-    if (!coded) return;
+// The work of one wave: MB idx of I slice task t. nb: 64 bytes of LDS of the wave's own
+// (top 16 | left 16 | ctop 2x8 | cleft 2x8).
+__device__ __forceinline__ void intra_prep_wave(const FrameArgs& a, const SliceTask& t, int idx, int mbx, int mby,
+                                                MbScratch& S, uint8_t* nb, const CavlcTables& T) {
     const int l = lane_id();
     const int b = l >> 2, r = l & 3;
     const int cl = l & 31, comp = cl >> 4, cb = (cl >> 2) & 3;
@@ -2328,11 +2432,14 @@ __global__ __launch_bounds__(256) void k_intra_prep(FrameArgs a) {
         wave_sync();
         const int lam = i4_lambda(t.qp);
         int total = 0;
+        // the modes chosen so far, 4 bits per block, in one register pair: MbInfo's two words,
+        // picked by the loop counter, would live in scratch
+        uint64_t modes = 0;
         for (int b = 0; b < 16; b++) {
             // i4_decide: neighbours in other MBs count as DC (2) when available
             const int bx = blk_x(b), by = blk_y(b);
-            const int ma = bx > 0 ? i4_mode(cand, blk_from_xy(bx - 1, by)) : (aL ? 2 : -1);
-            const int mt = by > 0 ? i4_mode(cand, blk_from_xy(bx, by - 1)) : (aT ? 2 : -1);
+            const int ma = bx > 0 ? (int)((modes >> (4 * blk_from_xy(bx - 1, by))) & 15) : (aL ? 2 : -1);
+            const int mt = by > 0 ? (int)((modes >> (4 * blk_from_xy(bx, by - 1))) & 15) : (aT ? 2 : -1);
             const int pm = i4_predicted(ma, mt);
             int best = 0x7fffffff, bm = I4_DC;
             for (int m = 0; m < 9; m++) {
@@ -2341,9 +2448,11 @@ __global__ __launch_bounds__(256) void k_intra_prep(FrameArgs a) {
                 const int cost = sd + lam * (m == pm ? 1 : 4);
                 if (cost < best) { best = cost; bm = m; }
             }
-            set_i4_mode(cand, b, bm);
+            modes |= (uint64_t)bm << (4 * b);
             total += best;
         }
+        cand.i4lo = (uint32_t)modes;
+        cand.i4hi = (uint32_t)(modes >> 32);
         i4 = i4_wins(total, sad16, t.qp);
         wave_sync();
     }
@@ -2376,10 +2485,60 @@ __global__ __launch_bounds__(256) void k_intra_prep(FrameArgs a) {
     }
 }
 
+// K6 inter and the K5 pre-pass in one launch: one wave per MB, 4 waves per workgroup (the CAVLC
+// tables are loaded once per 4 MBs). The wave of a P slice's MB codes it, the wave of an I
+// slice's MB runs the pre-pass, a SKIPALL slice's just records the skip; the branch is
+// wave-uniform and a frame without I slices pays no launch whose workgroups only exit.
+__global__ __launch_bounds__(256) void k_code_inter(FrameArgs a) {
+    if (a.gate && *a.gate == 0) return;   // CBR second pass not needed
+    __shared__ MbScratch Sw[4];
+    __shared__ QpelLds Qw[4];   // P: fractional-MV luma MC; I: the first 64 bytes hold the neighbour samples
+    __shared__ CavlcTables T;
+    const int w = threadIdx.x >> 6;
+    const int nmb = a.mb_w * a.mb_h;
+    const int idx = xcd_remap(blockIdx.x, gridDim.x) * 4 + w;
+    const bool valid = idx < nmb;
+    const int mbx = valid ? idx % a.mb_w : 0, mby = valid ? idx / a.mb_w : 0;
+    const int s = mby / a.rows_per_slice;
+    const SliceTask t = a.tasks[s];
+    if (valid && t.final_action == ACT_SKIPALL && lane_id() == 0) {
+        MbInfo z;
+        memset(&z, 0, sizeof(z));
+        a.mbs[idx] = z;
+        a.me[idx].mvx = 0;
+        a.me[idx].mvy = 0;
+        a.me[idx].ref = 0;
+        a.me[idx].fx = a.me[idx].fy = 0;
+    }
+    const bool is_p = valid && t.final_action == ACT_P, is_i = valid && t.final_action == ACT_I;
+    // The tables' dwords are requested now and reach LDS below, if the workgroup needs them:
+    // the load's latency lies under the fetch and the transform.
+    constexpr int kTabWords = (int)(sizeof(CavlcTables) / 4);
+    static_assert(kTabWords <= 512, "two dwords per thread");
+    const uint32_t* tab_src = reinterpret_cast<const uint32_t*>(a.cavlc_tabs);
+    const uint32_t tab0 = tab_src[threadIdx.x];
+    const uint32_t tab1 = threadIdx.x + 256 < kTabWords ? tab_src[threadIdx.x + 256] : 0u;
+    InterMb m;
+    bool need_tables = is_i;
+    if (is_p) need_tables = code_inter_begin(a, t, s, idx, mbx, mby, Sw[w], Qw[w], m) != 0;
+    // Only the size bounds and the pre-pass read the CAVLC tables: a workgroup whose MBs all have
+    // cbp 0 (or that has none to code) does not load them, the others load them behind the
+    // fetch and the transform. Every wave of the workgroup arrives here.
+    if (__syncthreads_or(need_tables)) {
+        uint32_t* tab_dst = reinterpret_cast<uint32_t*>(&T);
+        tab_dst[threadIdx.x] = tab0;
+        if (threadIdx.x + 256 < kTabWords) tab_dst[threadIdx.x + 256] = tab1;
+        __syncthreads();
+    }
+    static_assert(sizeof(QpelLds) >= 64, "the pre-pass keeps its neighbour samples in the wave's QpelLds");
+    if (is_p) code_inter_finish(a, t, idx, mbx, mby, Sw[w], T, m);
+    else if (is_i) intra_prep_wave(a, t, idx, mbx, mby, Sw[w], reinterpret_cast<uint8_t*>(&Qw[w]), T);
+}
+
 // ---------------------------------------------------------------------------
 // K5+K6 intra: one workgroup per I slice, wave w codes MB row w, MB x at step
 // t = x + 2w (wavefront); neighbour edges travel through LDS rings. Modes and the
-// start QP come from k_intra_prep, so a step is prediction, quantisation and
+// start QP come from the pre-pass (intra_prep_wave), so a step is prediction, quantisation and
 // reconstruction only; the next step's source rows and decisions are loaded ahead.
 constexpr int kMaxRows = 16;
 struct IntraEdges {
@@ -2596,7 +2755,7 @@ __global__ __launch_bounds__(64 * (MAXROWS + 1)) void k_code_intra(FrameArgs a) 
 // column only (kept in the wave's LDS), and the sub-slices of every slice run in
 // parallel (1080p: 17 slices x 12 sub-slices = 204 waves of at most 40 steps, where
 // k_code_intra's wavefront is 17 chains of 126 steps). Modes and start QPs come from
-// k_intra_prep; the next MB's source samples and decisions are loaded before the
+// the pre-pass; the next MB's source samples and decisions are loaded before the
 // current MB is coded.
 __global__ __launch_bounds__(256) void k_code_intra_sub(FrameArgs a) {
     if (a.gate && *a.gate == 0) return;   // CBR second pass not needed
@@ -2642,7 +2801,7 @@ __global__ __launch_bounds__(256) void k_code_intra_sub(FrameArgs a) {
         const int mode = __builtin_amdgcn_readfirstlane(pre.i16_mode);
         const int cmode = __builtin_amdgcn_readfirstlane(pre.chroma_mode);
         const int start_qp = __builtin_amdgcn_readfirstlane(pre.qp);
-        // k_intra_prep's choice for this MB: read before `pre` is overwritten by the prefetch
+        // the pre-pass's choice for this MB: read before `pre` is overwritten by the prefetch
         const bool is_i4 = __builtin_amdgcn_readfirstlane((int)pre.type) == MB_I4x4;
         const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)pre.i4lo);
         const uint32_t m1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)pre.i4hi);
@@ -3587,8 +3746,7 @@ void launch_rc_account(const FrameArgs& a, const int* sizes, int n, int stride, 
 // Transform / quantisation / reconstruction / CAVLC of every coded slice.
 static void launch_code(const FrameArgs& a, hipStream_t s) {
     int nmb = a.mb_w * a.mb_h;
-    hipLaunchKernelGGL(k_code_inter, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_intra_prep, dim3((nmb + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_code_inter, dim3((nmb + 3) / 4), dim3(256), 0, s, a);   // P slices, and the pre-pass of I slices
     // Every I slice of a geometry is coded by the same kernel (split_i depends on the
     // geometry alone): the sub-slice kernel where slices are split (K5, one wave per
     // sub-slice), the wavefront kernel elsewhere. The other one would only exit.
