@@ -642,7 +642,7 @@ std::vector<uint8_t> CpuAv1Encoder::assemble(const std::vector<std::vector<uint8
 void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, std::vector<h264::EncodedPacket>& out) {
     fe.load_frame(bgrx, stride);
     fe.ctl_.plan(fe.stripe_dirty.data(), fe.tasks.data());
-    if (fe.ltr_slots_) fe.ltr_plan();   // long-term cache (ltr.h, buffer map): one decision per tile row
+    if (fe.ltr_cfg.slots) fe.ltr_plan();   // long-term cache (ltr.h, buffer map): one decision per tile row
     const int ns = fe.g.num_slices;
     bool key = false;
     for (int s = 0; s < ns; s++) {
@@ -661,13 +661,11 @@ void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, s
     fe.ctl_.rate_control(fe.tasks.data(), fe.me.data());   // K10
     fp.key = key;
     fp.screen = key && palette_on;
-    if (fe.ltr_slots_) {   // the buffers the header names, from the map before this frame's commit
-        const ltr::LtrState& ls = fe.ltr_state[ns];
-        int slot = -1;
-        for (int s = 0; s < ns; s++) slot = sk_max(slot, fe.ltr_task[s].slot);   // one slot per frame (ltr_av1_reduce)
-        fp.last_buf = ltr::ltr_av1_last_buf(ls);
-        fp.last2_buf = slot >= 0 ? ls.st_fn[slot] : fp.last_buf;
-        fp.refresh = 1 << ltr::ltr_av1_new_buf(fe.ltr_slots_, ls, fe.ltr_task[0].store_slot);
+    if (fe.ltr_cfg.slots) {   // the buffers the header names, from the map before this frame's commit
+        const ltr::LtrAv1Bufs b = ltr::ltr_av1_frame_bufs(fe.ltr_cfg, fe.ltr_state[ns], fe.ltr_task.data(), ns);
+        fp.refresh = b.refresh;
+        fp.last_buf = b.last;
+        fp.last2_buf = b.last2;
     }
     uint8_t tab[52];
     for (int q = 0; q < 52; q++) tab[q] = (uint8_t)qidx_for_qp(q);

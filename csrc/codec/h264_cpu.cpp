@@ -36,12 +36,9 @@ CpuH264Encoder::CpuH264Encoder(const EncoderConfig& c) : cfg(c) {
     dbinfo.assign(g.num_mbs(), DbInfo());
     fs_mv.assign((size_t)g.num_mbs() * 2, 0);
     tasks.assign(g.num_slices, SliceTask());
-    ltr_slots_ = ltr_slots_of(cfg);
-    ltr_excl_ = ltr_slots_ > 0 && cfg.codec >= 1;
-    ltr_unit_ = ltr_unit_slices_of(cfg);
-    ltr_max_age_ = ltr_max_age_env();
-    if (ltr_slots_) {
-        for (int j = 0; j < ltr_slots_; j++)
+    ltr_cfg = ltr_config_of(cfg);
+    if (ltr_cfg.slots) {
+        for (int j = 0; j < ltr_cfg.slots; j++)
             for (int p = 0; p < 3; p++) ltr_planes[j][p].assign(p ? nc : ny, 0);
         ltr::LtrState z;
         ltr::ltr_state_reset(z);
@@ -53,12 +50,12 @@ CpuH264Encoder::CpuH264Encoder(const EncoderConfig& c) : cfg(c) {
     }
     if (cfg.fullframe) {
         param_sets.resize(1);
-        build_parameter_sets(g.W, g.H, cfg.full_range, cfg.fps, param_sets[0], cfg.num_refs, ltr_slots_);
+        build_parameter_sets(g.W, g.H, cfg.full_range, cfg.fps, param_sets[0], cfg.num_refs, ltr_cfg.slots);
     } else {
         param_sets.resize(g.num_slices);
         for (int s = 0; s < g.num_slices; s++)
             build_parameter_sets(g.W, g.slice_pix_h(s), cfg.full_range, cfg.fps, param_sets[s], cfg.num_refs,
-                                 ltr_slots_);
+                                 ltr_cfg.slots);
     }
 }
 
@@ -375,14 +372,15 @@ void CpuH264Encoder::decide_scenecut(int s) {
             ref1 += me[mby * g.mb_w + mbx].ref == 1;
         }
     if (t.allow_scenecut && inter > intra) t.final_action = ACT_I;
-    if (ltr_unit_) return;   // AV1: set with the decision (ltr_av1_reduce), clean slices of a matched tile row included
-    if (ltr_excl_) ltr_task[s].ref1_mbs = ltr::ltr_exclusive_mbs(ltr_task[s], t.final_action == ACT_P, t.num_rows * g.mb_w);
-    else if (ltr_slots_) ltr_task[s].ref1_mbs = t.final_action == ACT_P ? ref1 : 0;   // the stream's cur_slot (ltr_commit)
+    if (ltr_cfg.slots)
+        ltr_task[s].ref1_mbs = ltr::ltr_ref1_mbs(ltr_cfg, ltr_task[s], t.final_action == ACT_P, t.num_rows * g.mb_w, ref1);
 }
 
 // Long-term cache, once per frame between planning and motion search (k_ltr_match +
 // k_ltr_decide): dirty count of every stream, on a gated frame the zero-vector luma SADs
-// of its slices against the current reference and every valid slot, then ltr_decide.
+// of its slices against the current reference and every valid slot, then ltr_stream_decide.
+// As in k_ltr_match the gate sees the slots before this picture's expiry; a column taken for a
+// slot that expires now is never read (ltr_match).
 void CpuH264Encoder::ltr_plan() {
     const int ns = g.num_slices;
     auto decide = [&](ltr::LtrState& st, int s0, int s1) {
@@ -390,21 +388,18 @@ void CpuH264Encoder::ltr_plan() {
         const int n = (r1 - r0) * g.mb_w;
         int nd = 0;
         for (int j = r0 * g.mb_w; j < r1 * g.mb_w; j++) nd += mb_dirty[j] != 0;
-        bool planned_p = false, key = false;
+        bool anyp = false, key = false;
         for (int s = s0; s < s1; s++) {
-            planned_p |= tasks[s].action == ACT_P;
+            anyp |= tasks[s].action == ACT_P;
             key |= tasks[s].action == ACT_I;
         }
-        planned_p = planned_p && !key;
-        if (ltr_excl_ && !ltr_unit_) ltr::ltr_expire(ltr_slots_, st, tasks[s0].frame_num, ltr_max_age_);
-        // AV1 (ltr_unit_): the unit is the tile row, so every slice is compared, clean ones too
-        auto compared = [&](int s) { return ltr_unit_ ? planned_p : tasks[s].action == ACT_P; };
-        if (planned_p && ltr::ltr_large(nd, n) && st.valid) {
+        const bool gated = anyp && !key && ltr::ltr_large(nd, n) && st.valid;
+        if (gated) {
             for (int s = s0; s < s1; s++) {
-                if (!compared(s)) continue;
+                if (!ltr_slice_compared(ltr_cfg, tasks[s])) continue;
                 const size_t o0 = (size_t)tasks[s].first_row * 16 * g.stride_y;
                 const size_t cnt = (size_t)tasks[s].num_rows * 16 * g.stride_y;
-                for (int c = 0; c < 1 + ltr_slots_; c++) {
+                for (int c = 0; c < 1 + ltr_cfg.slots; c++) {
                     if (c > 0 && !((st.valid >> (c - 1)) & 1)) continue;
                     const uint8_t* r = (c ? ltr_planes[c - 1][0] : ref[0]).data() + o0;
                     const uint8_t* q = src[0].data() + o0;
@@ -413,14 +408,8 @@ void CpuH264Encoder::ltr_plan() {
                     ltr_sad[(size_t)s * ltr::kLtrSadCols + c] = sum;
                 }
             }
-            if (ltr_unit_) ltr::ltr_sum_units(ltr_slots_, st.valid, s0, s1, ltr_unit_, ltr_sad.data());
         }
-        ltr::ltr_decide(ltr_slots_, st, nd, n, planned_p, tasks[s0].frame_num, kFrameNumMask, s0, s1, compared,
-                        ltr_sad.data(), ltr_task.data());
-        if (ltr_unit_)
-            ltr::ltr_av1_reduce(ltr_slots_, s0, s1, [&](int s) { return tasks[s].num_rows * g.mb_w; }, ltr_task.data());
-        for (int s = s0; s < s1; s++)
-            if (ltr_task[s].slot >= 0 && !ltr_excl_) tasks[s].num_refs = 2;   // [previous picture, the slot]
+        ltr_stream_decide(ltr_cfg, st, tasks.data(), s0, s1, nd, g.mb_w, gated, ltr_sad.data(), ltr_task.data());
     };
     if (cfg.fullframe) decide(ltr_state[ns], 0, ns);
     else
@@ -784,12 +773,12 @@ std::vector<std::vector<uint8_t>> CpuH264Encoder::write_slice(int s) {
         h.slice_qp = t.qp;
         h.deblock = slice_deblock(cfg.deblock, t);
         h.num_refs = intra ? 1 : t.num_refs;
-        if (ltr_slots_) {
+        if (ltr_cfg.slots) {
             const ltr::LtrTask& L = ltr_task[s];
             if (t.final_action == ACT_P) h.lt_ref = L.slot;
             if (!h.idr && L.store_slot >= 0) {   // every slice NAL of the picture carries the same marking
                 h.lt_store = L.store_slot;
-                h.lt_max_idx = ltr_slots_;
+                h.lt_max_idx = ltr_cfg.slots;
                 h.st_drop = L.mmco1;
             }
         }
@@ -855,7 +844,7 @@ void CpuH264Encoder::finish_frame() {
     for (int s = 0; s < g.num_slices; s++) {
         const SliceTask& t = tasks[s];
         const int y0 = t.first_row * 16, y1 = (t.first_row + t.num_rows) * 16;
-        if (ltr_slots_ && ltr_task[s].store_slot >= 0) {
+        if (ltr_cfg.slots && ltr_task[s].store_slot >= 0) {
             // long-term store: the previous picture's rows, before the new reconstruction replaces them
             std::vector<uint8_t>* slot = ltr_planes[ltr_task[s].store_slot];
             memcpy(&slot[0][(size_t)y0 * g.stride_y], &ref[0][(size_t)y0 * g.stride_y], (size_t)(y1 - y0) * g.stride_y);
@@ -898,23 +887,12 @@ void CpuH264Encoder::finish_frame() {
             }
     }
     for (int p = 0; p < 3; p++) prev[p].swap(src[p]);
-    if (ltr_slots_) {
-        const int ns = g.num_slices;
-        if (ltr_unit_) {
-            ltr::ltr_commit_av1(ltr_slots_, ltr_state[ns], ctl_.picture_is_idr(tasks.data()), g.num_mbs(), 0, ns,
-                                ltr_task.data());
-        } else if (ltr_excl_) {
-            ltr::ltr_commit_rps(ltr_slots_, ltr_state[ns], ctl_.picture_is_idr(tasks.data()), tasks[0].frame_num,
-                                g.num_mbs(), 0, ns, ltr_task.data());
-        } else if (cfg.fullframe) {
-            ltr::ltr_commit(ltr_slots_, ltr_state[ns], true, ctl_.picture_is_idr(tasks.data()), tasks[0].frame_num,
-                            g.num_mbs(), 0, ns, ltr_task.data());
-        } else {
-            for (int s = 0; s < ns; s++)
-                ltr::ltr_commit(ltr_slots_, ltr_state[s], tasks[s].final_action != ACT_NONE,
-                                tasks[s].final_action == ACT_I && tasks[s].idr_on_intra, tasks[s].frame_num,
-                                tasks[s].num_rows * g.mb_w, s, s + 1, ltr_task.data());
-        }
+    if (ltr_cfg.slots) {
+        const int ns = g.num_slices, ff = cfg.fullframe;
+        const bool idr = ff && ctl_.picture_is_idr(tasks.data());
+        for (int s = 0; s < (ff ? 1 : ns); s++)   // one stream: the picture, or every stripe
+            ltr_stream_commit(ltr_cfg, ltr_state[ff ? ns : s], tasks.data(), ltr_task.data(), s, ff ? ns : s + 1, g.mb_w,
+                              g.num_mbs(), ff, idr);
     }
     ctl_.commit(tasks.data());
     first_frame = false;
@@ -947,7 +925,7 @@ void CpuH264Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id,
         st.subpel_prev = st.subpel_hits;
         st.subpel_hits = 0;
     }
-    if (ltr_slots_) ltr_plan();
+    if (ltr_cfg.slots) ltr_plan();
     for (int s = 0; s < g.num_slices; s++)
         if (tasks[s].action == ACT_P) {
             motion_search(s);
@@ -1008,7 +986,7 @@ static void* state_section_ptr(CpuH264Encoder& e, const StateSection& s) {
 }
 
 void cpu_export_state(CpuH264Encoder& e, void* dst) {
-    state_sections(e.g, e.ltr_slots_, [&](const StateSection& s) {
+    state_sections(e.g, e.ltr_cfg.slots, [&](const StateSection& s) {
         uint8_t* o = static_cast<uint8_t*>(dst) + s.off;
         if (s.kind == ST_HEADER) {
             StateHeader h;
@@ -1026,7 +1004,7 @@ bool cpu_import_state(CpuH264Encoder& e, const void* src) {
     StateHeader h;
     memcpy(&h, src, sizeof(h));
     if (!state_header_matches(e.cfg, e.g, h)) return false;
-    state_sections(e.g, e.ltr_slots_, [&](const StateSection& s) {
+    state_sections(e.g, e.ltr_cfg.slots, [&](const StateSection& s) {
         const uint8_t* i = static_cast<const uint8_t*>(src) + s.off;
         if (s.kind == ST_STRIPES) e.ctl_.import_states(reinterpret_cast<const StripeState*>(i));
         else if (s.kind != ST_HEADER) memcpy(state_section_ptr(e, s), i, s.bytes);

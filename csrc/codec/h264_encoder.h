@@ -70,17 +70,23 @@ inline int ltr_slots_of(const EncoderConfig& c) {
     return c.ltr_slots > 0 ? (c.ltr_slots < cap ? c.ltr_slots : cap) : 0;
 }
 
-// AV1: front-end slices in one tile row, the cache's decision unit (0: the slice is the unit).
-inline int ltr_unit_slices_of(const EncoderConfig& c) {
-    if (c.codec != 2 || ltr_slots_of(c) == 0) return 0;
-    return av1::tile_row_units(c.width, c.height, c.tile_cols_log2, c.tile_rows_log2) / (c.stripe_height / 16);
-}
-
 // HEVC cache expiry age in pictures (ltr.h ltr_expire): SK_HEVC_LTR_MAX_AGE=<n>, clipped to
 // 2..32768 (tests exercise expiry at small sizes); read once when an encoder is built.
 inline int ltr_max_age_env() {
     const char* e = getenv("SK_HEVC_LTR_MAX_AGE");
     return e && e[0] ? ltr::ltr_clip_max_age(atoi(e)) : ltr::kLtrMaxAge;
+}
+
+// The session's cache (ltr.h LtrConfig), for both back ends: the one place a codec maps to a mode.
+inline ltr::LtrConfig ltr_config_of(const EncoderConfig& c) {
+    ltr::LtrConfig l = {};
+    l.slots = ltr_slots_of(c);
+    if (!l.slots) return l;
+    l.mode = c.codec == 2 ? ltr::LTR_BUFMAP : c.codec == 1 ? ltr::LTR_RPS : ltr::LTR_SECOND_REF;
+    if (l.mode == ltr::LTR_BUFMAP)   // front-end slices in one tile row, the cache's decision unit
+        l.unit_slices = av1::tile_row_units(c.width, c.height, c.tile_cols_log2, c.tile_rows_log2) / (c.stripe_height / 16);
+    l.max_age = ltr_max_age_env();
+    return l;
 }
 
 // Why a configuration cannot run the long-term cache (nullptr: it can, or the cache is off).
@@ -329,6 +335,48 @@ SK_HD void commit_picture(StripeState& pic, bool idr, int max_refs) {
         pic.frame_num = (pic.frame_num + 1) & kFrameNumMask;
         pic.refs = pic.refs + 1 < max_refs ? pic.refs + 1 : max_refs;
     }
+}
+
+// ---- long-term cache (ltr.h) over a stream's SliceTasks: slices [s0, s1) of one decoder ----
+// Whether a gated frame takes slice t's zero-vector SADs: the slices planned as P; LTR_BUFMAP:
+// every slice, the tile row is the unit and its clean slices count too.
+SK_HD bool ltr_slice_compared(const ltr::LtrConfig& c, const SliceTask& t) {
+    return c.mode == ltr::LTR_BUFMAP || t.action == ACT_P;
+}
+
+// The stream's decision for one frame, between planning and motion search. `dirty`: changed
+// macroblocks of the stream; `gated`: `sad` ([slice][kLtrSadCols]) holds this frame's sums
+// of the compared slices. Fills lt[s0..s1) and gives a matched H.264 slice its second reference.
+SK_HD void ltr_stream_decide(const ltr::LtrConfig& c, ltr::LtrState& st, SliceTask* tasks, int s0, int s1, int dirty,
+                             int mb_w, bool gated, uint32_t* sad, ltr::LtrTask* lt) {
+    bool key = false, anyp = false;
+    int rows = 0;
+    for (int s = s0; s < s1; s++) {
+        key |= tasks[s].action == ACT_I;
+        anyp |= tasks[s].action == ACT_P;
+        rows += tasks[s].num_rows;
+    }
+    if (c.mode == ltr::LTR_RPS) ltr::ltr_expire(c.slots, st, tasks[s0].frame_num, c.max_age);
+    if (c.mode == ltr::LTR_BUFMAP && gated)   // one sum per tile row, so its slices match the same slot
+        ltr::ltr_sum_units(c.slots, st.valid, s0, s1, c.unit_slices, sad);
+    ltr::ltr_decide(c.slots, st, dirty, rows * mb_w, anyp && !key, tasks[s0].frame_num, kFrameNumMask, s0, s1,
+                    [&](int s) { return ltr_slice_compared(c, tasks[s]); }, sad, lt);
+    if (c.mode == ltr::LTR_BUFMAP)   // one slot per frame; ref1_mbs of every slice, clean ones included
+        ltr::ltr_av1_reduce(c.slots, s0, s1, [&](int s) { return tasks[s].num_rows * mb_w; }, lt);
+    if (c.mode == ltr::LTR_SECOND_REF)
+        for (int s = s0; s < s1; s++)
+            if (lt[s].slot >= 0) tasks[s].num_refs = 2;   // [previous picture, the slot]
+}
+
+// The stream's state after its picture was coded. A picture's stream (`fullframe`; HEVC and
+// AV1 always) always codes one, an IDR or key frame when `picture_idr`; a stripe's says so itself.
+SK_HD void ltr_stream_commit(const ltr::LtrConfig& c, ltr::LtrState& st, const SliceTask* tasks, const ltr::LtrTask* lt,
+                             int s0, int s1, int mb_w, int num_mbs, bool fullframe, bool picture_idr) {
+    const SliceTask& t = tasks[s0];
+    if (fullframe) ltr::ltr_commit(c, st, true, picture_idr, t.frame_num, num_mbs, s0, s1, lt);
+    else
+        ltr::ltr_commit(c, st, t.final_action != ACT_NONE, t.final_action == ACT_I && t.idr_on_intra, t.frame_num,
+                        t.num_rows * mb_w, s0, s1, lt);
 }
 
 struct MeResult;

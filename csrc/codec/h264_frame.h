@@ -103,13 +103,10 @@ class CpuH264Encoder {
     std::vector<uint8_t> ref1[3];  // second reference (previous-but-one picture) when num_refs == 2
     // Long-term reference cache (cfg.ltr_slots, ltr.h): plane sets (a stripe's slot j lives at the stripe's
     // rows of set j), the per-stream state ([num_slices] stripes, then the picture's) and the per-slice decisions
-    int ltr_slots_ = 0;
-    bool ltr_excl_ = false;   // HEVC, AV1: a matched slice predicts from its slot alone (ltr.h exclusive mode)
-    int ltr_unit_ = 0;        // AV1: slices per tile row, the decision unit (ltr.h buffer map); 0: the slice
-    int ltr_max_age_ = ltr::kLtrMaxAge;   // exclusive mode: expiry age in pictures (SK_HEVC_LTR_MAX_AGE)
-    // reference index 0 of slice s: its slot's planes in exclusive mode when it matched, else the previous picture
+    ltr::LtrConfig ltr_cfg = {};   // ltr_config_of(cfg); slots == 0: off
+    // reference index 0 of slice s: its slot's planes in the exclusive modes when it matched, else the previous picture
     const std::vector<uint8_t>* ref0(int s) const {
-        return ltr_excl_ && ltr_task[s].slot >= 0 ? ltr_planes[ltr_task[s].slot] : ref;
+        return ltr_cfg.mode != ltr::LTR_SECOND_REF && ltr_task[s].slot >= 0 ? ltr_planes[ltr_task[s].slot] : ref;
     }
     std::vector<uint8_t> ltr_planes[ltr::kLtrMaxSlots][3];
     std::vector<ltr::LtrState> ltr_state;
@@ -150,7 +147,7 @@ class CpuH264Encoder {
     // reference index 1 of slice t: the slice's cached picture (long-term cache), else the previous-but-one
     const std::vector<uint8_t>* refs(int refi, const SliceTask& t) const {
         if (!refi) return ref0(t.first_row / g.rows_per_slice);
-        return ltr_slots_ ? ltr_planes[sk_max(ltr_task[t.first_row / g.rows_per_slice].slot, 0)] : ref1;
+        return ltr_cfg.slots ? ltr_planes[sk_max(ltr_task[t.first_row / g.rows_per_slice].slot, 0)] : ref1;
     }
     void full_search(int mbx, int mby, const SliceTask& t, int16_t* out) const;
 };

@@ -93,7 +93,7 @@ inline bool state_header_matches(const EncoderConfig& c, const Geometry& g, cons
            h.stripe_height == c.stripe_height && h.fullframe == c.fullframe && h.num_slices == g.num_slices;
 }
 
-// The CPU encoder's state into / out of a host blob of state_bytes(e.g, e.ltr_slots_) bytes
+// The CPU encoder's state into / out of a host blob of state_bytes(e.g, e.ltr_cfg.slots) bytes
 // (h264_cpu.cpp). HEVC / AV1 keep all their inter-frame state in the shared front end, itself a
 // CpuH264Encoder. Import returns false, and changes nothing, when the header does not match.
 class CpuH264Encoder;

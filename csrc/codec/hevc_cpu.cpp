@@ -141,7 +141,7 @@ CpuHevcEncoder::CpuHevcEncoder(const h264::EncoderConfig& cfg) : fe(front_config
     sao.assign(nc, SaoParams{});
     sao_cost.assign(nc, 0);
     sao_md.assign((size_t)nc * kSaoMd, 0);
-    build_parameter_sets(fe.g.W, fe.g.H, cfg.full_range, cfg.fps, param_sets, fe.ltr_slots_);
+    build_parameter_sets(fe.g.W, fe.g.H, cfg.full_range, cfg.fps, param_sets, fe.ltr_cfg.slots);
     seg_k = intra_seg_k(geo.ctb_w, geo.ctb_h);
 }
 
@@ -882,7 +882,7 @@ std::vector<uint8_t> CpuHevcEncoder::write_segment(const SliceTask& t, int cy0, 
     h.qp_delta = t.qp - 26;
     h.num_entry = rows - 1;
     h.entry = esc.data();
-    if (fe.ltr_slots_) {   // long-term cache: the RPS of every slice, list 0 of a matched P slice
+    if (fe.ltr_cfg.slots) {   // long-term cache: the RPS of every slice, list 0 of a matched P slice
         const ltr::LtrState& ls = fe.ltr_state[geo.num_slices];   // after this picture's expiry, before its commit
         h.lt_present = 1;
         h.lt_valid = ls.valid;
@@ -921,7 +921,7 @@ void CpuHevcEncoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id,
         st.subpel_prev = st.subpel_hits;
         st.subpel_hits = 0;
     }
-    if (fe.ltr_slots_) fe.ltr_plan();   // long-term cache (ltr.h, exclusive mode): expiry, match, store
+    if (fe.ltr_cfg.slots) fe.ltr_plan();   // long-term cache (ltr.h, exclusive mode): expiry, match, store
     const int ns = geo.num_slices;
     for (int s = 0; s < ns; s++)
         if (fe.tasks[s].action == ACT_P) {

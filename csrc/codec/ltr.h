@@ -1,12 +1,21 @@
 // Long-term reference cache: the policy that decides which reconstructed pictures a
 // stream keeps beyond its sliding window, when a slice predicts from one of them, and
-// the model of the decoder's reference marking that keeps the stream inside its DPB.
-// POD state and SK_HD functions only, codec-agnostic (frame numbers are the codec's
-// picture counter modulo `fn_mask + 1`), so the CPU back end and the GPU frame graph run
-// the same code and a later codec can reuse it.
+// the model of the decoder's reference bookkeeping that keeps the stream inside its DPB.
+// POD state and SK_HD functions only (frame numbers are the codec's picture counter modulo
+// `fn_mask + 1`), so the CPU back end and the GPU frame graph run the same code.
 //
 // A stream is what owns a decoder: a stripe in striped mode, the picture in full-frame
 // mode. All quantities are integers, so both back ends decide identically.
+//
+// LtrConfig is a session's cache: the slot count (0: off), the expiry age and the LtrMode,
+// which says how the codec names a cached picture (H.264: second reference and marking
+// model; HEVC: exclusive, RPS; AV1: exclusive, buffer map, tile rows). It is derived once,
+// by ltr_config_of (h264_encoder.h). Entry points, one of each for all modes:
+//   ltr_decide   the stream's decision for one frame, before motion search
+//   ltr_commit   the stream's state after its picture was coded; the mode selects the tail
+//   ltr_av1_frame_bufs   the buffers an AV1 frame header names
+// ltr_stream_decide, ltr_stream_commit and ltr_ref1_mbs (h264_encoder.h) wrap them with what
+// a stream's SliceTasks say; every back end calls those.
 #pragma once
 #include <stdint.h>
 #include "sk_common.h"
@@ -19,6 +28,21 @@ constexpr int kLtrSettle = 8;      // consecutive quiet frames after which a str
 constexpr int kLtrQuietDen = 16;   // quiet frame: dirty MBs < 1/16 of the stream's MBs
 constexpr int kLtrLargeDen = 4;    // large change: dirty MBs >= 1/4 of the stream's MBs
 constexpr int kLtrSadCols = 1 + kLtrMaxSlots;   // per slice: SAD against the current reference, then each slot
+
+// How the codec names a cached picture.
+enum LtrMode : int32_t {
+    LTR_SECOND_REF = 0,   // H.264: the slot is reference index 1, next to the previous picture; marking model (8.2.5)
+    LTR_RPS = 1,          // HEVC: exclusive (a matched slice predicts from its slot alone), POC table, expiry
+    LTR_BUFMAP = 2,       // AV1: exclusive, the decoder's buffer map, the tile row is the decision unit
+};
+
+// A session's cache. slots == 0: off, and the other fields are 0.
+struct LtrConfig {
+    int32_t slots;         // pictures kept per stream
+    int32_t mode;          // LtrMode
+    int32_t unit_slices;   // LTR_BUFMAP: front-end slices in one tile row
+    int32_t max_age;       // LTR_RPS: expiry age in pictures (ltr_expire)
+};
 
 // Per stream, carried from frame to frame (and in the version-4 state blob).
 struct LtrState {
@@ -142,48 +166,7 @@ SK_HD void ltr_decide(int slots, LtrState& st, int dirty, int mbs, bool planned_
     }
 }
 
-// After the stream's picture was coded (`coded`: it produced a picture at all; `idr`: an
-// IDR picture): current-content slot from the per-slice reference counts, then the
-// marking model follows what the decoder does with the picture's dec_ref_pic_marking().
-SK_HD void ltr_commit(int slots, LtrState& st, bool coded, bool idr, int frame_num, int mbs, int s0, int s1,
-                      const LtrTask* lt) {
-    if (!coded) return;
-    if (idr) {   // an IDR empties the DPB: no long-term pictures, one short-term (frame_num 0)
-        const int q = st.quiet_run;
-        ltr_state_reset(st);
-        st.quiet_run = q;
-        st.n_st = 1;
-        st.st_fn[0] = 0;
-        return;
-    }
-    const LtrTask& f = lt[s0];
-    if (f.flags & LTR_GATED) {
-        st.cur_slot = -1;
-        for (int j = slots - 1; j >= 0; j--) {
-            int cnt = 0;
-            for (int s = s0; s < s1; s++)
-                if (lt[s].slot == j) cnt += lt[s].ref1_mbs;
-            if (2 * cnt >= mbs) st.cur_slot = j;
-        }
-        if (st.cur_slot >= 0 && st.cur_slot == f.store_slot) st.cur_slot = -1;   // the slot now holds the previous content
-    } else if (f.flags & LTR_DRIFT) {
-        st.cur_slot = -1;   // neither quiet nor a switch: the content moved away from the slot's
-    }
-    if (f.store_slot >= 0) {
-        if (f.mmco1 >= 0) {   // MMCO 1: the oldest short-term picture
-            for (int k = 1; k < st.n_st; k++) st.st_fn[k - 1] = st.st_fn[k];
-            st.n_st--;
-        }
-        st.n_st--;            // MMCO 3: the previous picture (the newest short-term one) turns long-term
-        st.valid |= 1 << f.store_slot;
-    } else if (st.n_st + ltr_popcount(st.valid) >= 1 + slots && st.n_st > 0) {
-        for (int k = 1; k < st.n_st; k++) st.st_fn[k - 1] = st.st_fn[k];   // sliding window (8.2.5.3)
-        st.n_st--;
-    }
-    st.st_fn[st.n_st++] = frame_num;
-}
-
-// ---- exclusive mode (HEVC) ----------------------------------------------------------
+// ---- LTR_RPS (HEVC) -------------------------------------------------------------------
 // A matched slice predicts from its slot alone (reference index 0 of a one-entry list), so
 // the slice keeps one reference and every unit coded as P counts for the slot. An RPS names
 // every picture the decoder keeps, so no marking model is needed; the free fields hold
@@ -206,41 +189,17 @@ SK_HD void ltr_expire(int slots, LtrState& st, int poc, int max_age) {
         }
 }
 
-// ref1_mbs of a slice in exclusive mode: all of its `mbs` units when it matched a slot and
-// is coded as P.
-SK_HD int ltr_exclusive_mbs(const LtrTask& t, bool coded_p, int mbs) { return t.slot >= 0 && coded_p ? mbs : 0; }
-
-// ltr_commit for a stream whose pictures carry an RPS (`poc`: POC LSBs of the picture just
-// coded; the stored picture is the one before it). An IDR empties the cache.
-SK_HD void ltr_commit_rps(int slots, LtrState& st, bool idr, int poc, int mbs, int s0, int s1, const LtrTask* lt) {
-    if (idr) {
-        const int q = st.quiet_run;
-        ltr_state_reset(st);
-        st.quiet_run = q;
-        st.n_st = 1;
-        return;
-    }
-    const LtrTask& f = lt[s0];
-    if (f.flags & LTR_GATED) {
-        st.cur_slot = -1;
-        for (int j = slots - 1; j >= 0; j--) {
-            int cnt = 0;
-            for (int s = s0; s < s1; s++)
-                if (lt[s].slot == j) cnt += lt[s].ref1_mbs;
-            if (2 * cnt >= mbs) st.cur_slot = j;
-        }
-        if (st.cur_slot >= 0 && st.cur_slot == f.store_slot) st.cur_slot = -1;   // the slot now holds the previous content
-    } else if (f.flags & LTR_DRIFT) {
-        st.cur_slot = -1;
-    }
-    if (f.store_slot >= 0) {
-        st.valid |= 1 << f.store_slot;
-        st.st_fn[f.store_slot] = (poc - 1) & kLtrPocMask;
-    }
-    st.n_st = 1;
+// ref1_mbs of a slice once its scene-cut decision is known (`coded_p`: it is coded as P;
+// `counted_ref1`: its macroblocks whose vector points at reference index 1). Exclusive
+// modes: all of its `slice_mbs` units when it matched a slot; LTR_BUFMAP set that with the
+// decision already (ltr_av1_reduce: clean slices of a matched tile row count too).
+SK_HD int ltr_ref1_mbs(const LtrConfig& c, const LtrTask& t, bool coded_p, int slice_mbs, int counted_ref1) {
+    if (c.mode == LTR_BUFMAP) return t.ref1_mbs;
+    if (c.mode == LTR_RPS) return t.slot >= 0 && coded_p ? slice_mbs : 0;
+    return coded_p ? counted_ref1 : 0;   // the stream's cur_slot (ltr_commit)
 }
 
-// ---- exclusive mode with a buffer map (AV1) -------------------------------------------
+// ---- LTR_BUFMAP (AV1) -----------------------------------------------------------------
 // An AV1 decoder owns eight reference buffers and a frame header names the ones it reads
 // and writes, so a cached picture is a buffer that later frames leave alone. A picture
 // cannot be moved after it was decoded: storing the previous picture into slot k means
@@ -304,10 +263,29 @@ SK_HD int ltr_av1_reduce(int slots, int s0, int s1, Units units, LtrTask* lt) {
     return best;
 }
 
-// ltr_commit for a stream whose cache is the buffer map (`key`: a key frame, which refreshes
-// all eight buffers: the cache is empty and the picture is in buffer 0).
-SK_HD void ltr_commit_av1(int slots, LtrState& st, bool key, int mbs, int s0, int s1, const LtrTask* lt) {
-    if (key) {
+// The buffers an inter frame's header names, from the map before the frame's commit and the
+// decisions of its `ns` slices: the one it is written to, the previous picture's (LAST) and
+// the frame's slot's (LAST2; the previous picture's again without a slot).
+struct LtrAv1Bufs {
+    int refresh;   // refresh_frame_flags
+    int last, last2;
+};
+SK_HD LtrAv1Bufs ltr_av1_frame_bufs(const LtrConfig& c, const LtrState& st, const LtrTask* lt, int ns) {
+    int slot = -1;
+    for (int s = 0; s < ns; s++) slot = sk_max(slot, lt[s].slot);   // one slot per frame (ltr_av1_reduce)
+    const int last = ltr_av1_last_buf(st);
+    return LtrAv1Bufs{1 << ltr_av1_new_buf(c.slots, st, lt[0].store_slot), last, slot >= 0 ? st.st_fn[slot] : last};
+}
+
+// ---- all modes ------------------------------------------------------------------------
+// After the stream's picture was coded (`coded`: it produced a picture at all; `idr`: an
+// IDR picture or a key frame; `fn`: its frame_num, LTR_RPS: its POC LSBs): the
+// current-content slot from the per-slice reference counts, then the decoder's bookkeeping
+// in the mode's terms.
+SK_HD void ltr_commit(const LtrConfig& c, LtrState& st, bool coded, bool idr, int fn, int mbs, int s0, int s1,
+                      const LtrTask* lt) {
+    if (!coded) return;
+    if (idr) {   // empties the cache; one previous picture (H.264: short-term, frame_num 0; AV1: in buffer 0)
         const int q = st.quiet_run;
         ltr_state_reset(st);
         st.quiet_run = q;
@@ -317,7 +295,7 @@ SK_HD void ltr_commit_av1(int slots, LtrState& st, bool key, int mbs, int s0, in
     const LtrTask& f = lt[s0];
     if (f.flags & LTR_GATED) {
         st.cur_slot = -1;
-        for (int j = slots - 1; j >= 0; j--) {
+        for (int j = c.slots - 1; j >= 0; j--) {
             int cnt = 0;
             for (int s = s0; s < s1; s++)
                 if (lt[s].slot == j) cnt += lt[s].ref1_mbs;
@@ -325,13 +303,32 @@ SK_HD void ltr_commit_av1(int slots, LtrState& st, bool key, int mbs, int s0, in
         }
         if (st.cur_slot >= 0 && st.cur_slot == f.store_slot) st.cur_slot = -1;   // the slot now holds the previous content
     } else if (f.flags & LTR_DRIFT) {
-        st.cur_slot = -1;
+        st.cur_slot = -1;   // neither quiet nor a switch: the content moved away from the slot's
+    }
+    if (c.mode == LTR_SECOND_REF) {   // what the decoder does with the picture's dec_ref_pic_marking()
+        if (f.store_slot >= 0) {
+            if (f.mmco1 >= 0) {   // MMCO 1: the oldest short-term picture
+                for (int k = 1; k < st.n_st; k++) st.st_fn[k - 1] = st.st_fn[k];
+                st.n_st--;
+            }
+            st.n_st--;            // MMCO 3: the previous picture (the newest short-term one) turns long-term
+            st.valid |= 1 << f.store_slot;
+        } else if (st.n_st + ltr_popcount(st.valid) >= 1 + c.slots && st.n_st > 0) {
+            for (int k = 1; k < st.n_st; k++) st.st_fn[k - 1] = st.st_fn[k];   // sliding window (8.2.5.3)
+            st.n_st--;
+        }
+        st.st_fn[st.n_st++] = fn;
+        return;
     }
     if (f.store_slot >= 0) {
-        const int nb = ltr_av1_new_buf(slots, st, f.store_slot);
-        st.st_fn[f.store_slot] = ltr_av1_last_buf(st);   // the previous picture stays where it is
+        if (c.mode == LTR_RPS) {   // the stored picture is the one before this
+            st.st_fn[f.store_slot] = (fn - 1) & kLtrPocMask;
+        } else {
+            const int nb = ltr_av1_new_buf(c.slots, st, f.store_slot);   // read before the map moves
+            st.st_fn[f.store_slot] = ltr_av1_last_buf(st);   // the previous picture stays where it is
+            st.st_fn[kLtrMaxSlots] = nb;
+        }
         st.valid |= 1 << f.store_slot;
-        st.st_fn[kLtrMaxSlots] = nb;
     }
     st.n_st = 1;
 }

@@ -468,14 +468,11 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
         A.frame_host[2] = lvl;
         // long-term cache (ltr.h buffer map): the buffers the frame header names, from the map
         // before this frame's commit (k_plan of the next frame); off: the host keeps buffer 0
-        if (f.ltr_unit) {
-            const ltr::LtrState& ls = f.ltr_state[ns];
-            int slot = -1;
-            for (int s = 0; s < ns; s++) slot = sk_max(slot, f.ltr_task[s].slot);   // one slot per frame (ltr_av1_reduce)
-            const int last = ltr::ltr_av1_last_buf(ls);
-            A.frame_host[3] = 1 << ltr::ltr_av1_new_buf(f.ltr_slots, ls, f.ltr_task[0].store_slot);
-            A.frame_host[4] = last;
-            A.frame_host[5] = slot >= 0 ? ls.st_fn[slot] : last;
+        if (f.ltr_cfg.mode == ltr::LTR_BUFMAP) {
+            const ltr::LtrAv1Bufs b = ltr::ltr_av1_frame_bufs(f.ltr_cfg, f.ltr_state[ns], f.ltr_task, ns);
+            A.frame_host[3] = b.refresh;
+            A.frame_host[4] = b.last;
+            A.frame_host[5] = b.last2;
         }
     }
 }
@@ -1780,7 +1777,7 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_modes, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_rec, dim3(tiles), dim3(1024), 0, s, a);
-    if (a.f.ltr_excl) hipLaunchKernelGGL(k_av1_inter<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    if (a.f.ltr_cfg.mode == ltr::LTR_BUFMAP) hipLaunchKernelGGL(k_av1_inter<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_av1_inter<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_merge, dim3(a.geo.sb_cols * a.geo.sb_rows), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_av1_modes, dim3((a.geo.c8 * a.geo.r8 + 255) / 256), dim3(256), 0, s, a);

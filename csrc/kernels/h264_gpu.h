@@ -81,9 +81,9 @@ struct FrameArgs {
     // 2 * ((W+1)/2)); yuv_fmt 0: BGRx input through k_convert_damage
     const uint8_t* yuv;
     int yuv_fmt;
-    // Long-term reference cache (codec/ltr.h), ltr_slots > 0. Slot j's planes lie at
+    // Long-term reference cache (codec/ltr.h), ltr_cfg.slots > 0. Slot j's planes lie at
     // ltr.y + j * ltr_ny and ltr.u / ltr.v + j * ltr_nc (a stripe's slot at the stripe's rows).
-    int ltr_slots;
+    ltr::LtrConfig ltr_cfg;     // ltr_config_of(cfg), as the CPU back end holds it
     Planes ltr;
     size_t ltr_ny, ltr_nc;
     ltr::LtrState* ltr_state;   // [num_slices + 1] per stream (last = the picture's, full-frame mode)
@@ -91,18 +91,15 @@ struct FrameArgs {
     uint32_t* ltr_part;         // [num_slices][kLtrSadCols][rows_per_slice] zero-vector SADs per MB row (k_ltr_match)
     uint32_t* ltr_sad;          // [num_slices][kLtrSadCols] their sums (k_ltr_decide)
     int* ltr_cnt;               // [num_slices][2] the slice's stream: dirty MBs, SADs computed (gated frame)
-    int ltr_excl;               // HEVC, AV1: a matched slice predicts from its slot alone (ltr.h exclusive mode)
-    int ltr_unit;               // AV1: slices per tile row, the decision unit (ltr.h buffer map); 0: the slice
-    int ltr_max_age;            // exclusive mode: expiry age in pictures (ltr_expire)
 };
 
 #if defined(__HIPCC__)
-// Reference index 0 of slice s: the previous picture, or in exclusive mode (HEVC and AV1, ltr.h) the
+// Reference index 0 of slice s: the previous picture, or in the exclusive modes (HEVC and AV1, ltr.h) the
 // cached picture a matched slice predicts from. s must be wave-uniform: the slot index goes
 // through readfirstlane, so the three base pointers are scalars (no per-lane select, no
 // indexed Planes array, which would live in scratch).
 __device__ __forceinline__ Planes ref0_planes(const FrameArgs& a, int s) {
-    if (!a.ltr_excl) return a.ref;
+    if (a.ltr_cfg.mode == ltr::LTR_SECOND_REF) return a.ref;
     const int j = __builtin_amdgcn_readfirstlane(a.ltr_task[s].slot);
     if (j < 0) return a.ref;
     return Planes{a.ltr.y + (size_t)j * a.ltr_ny, a.ltr.u + (size_t)j * a.ltr_nc, a.ltr.v + (size_t)j * a.ltr_nc};

@@ -61,7 +61,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 // Reference index 1 of slice s: the cached picture the slice chose (long-term cache, ltr.h),
 // else the previous-but-one picture.
 __device__ __forceinline__ Planes ref1_planes(const FrameArgs& a, int s) {
-    if (!a.ltr_slots) return a.ref1;
+    if (!a.ltr_cfg.slots) return a.ref1;
     const size_t j = (size_t)sk_max(a.ltr_task[s].slot, 0);
     return Planes{a.ltr.y + j * a.ltr_ny, a.ltr.u + j * a.ltr_nc, a.ltr.v + j * a.ltr_nc};
 }
@@ -900,22 +900,13 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
             for (int s = tid; s < ns; s += 256) idr &= a.tasks[s].final_action == ACT_I && a.tasks[s].idr_on_intra;
             idr = __syncthreads_and(idr);
             if (tid == 0) commit_picture(pic, idr, a.plan_cfg.num_refs);
-            if (a.ltr_unit && tid == 0)   // AV1: the cache is the decoder's buffer map (ltr.h)
-                ltr::ltr_commit_av1(a.ltr_slots, a.ltr_state[ns], idr, a.mb_w * a.mb_h, 0, ns, a.ltr_task);
-            else if (a.ltr_excl && tid == 0)   // HEVC: the cache follows the picture's RPS (ltr.h)
-                ltr::ltr_commit_rps(a.ltr_slots, a.ltr_state[ns], idr, a.tasks[0].frame_num, a.mb_w * a.mb_h, 0, ns,
-                                    a.ltr_task);
-            else if (a.ltr_slots && tid == 0)   // long-term cache: current slot and the marking model (ltr.h)
-                ltr::ltr_commit(a.ltr_slots, a.ltr_state[ns], true, idr, a.tasks[0].frame_num, a.mb_w * a.mb_h, 0, ns,
-                                a.ltr_task);
+            if (a.ltr_cfg.slots && tid == 0)   // long-term cache: the picture's stream (ltr.h)
+                ltr_stream_commit(a.ltr_cfg, a.ltr_state[ns], a.tasks, a.ltr_task, 0, ns, a.mb_w, a.mb_w * a.mb_h, true, idr);
         } else {
-            if (a.ltr_slots)
-                for (int s = tid; s < ns; s += 256) {
-                    const SliceTask& t = a.tasks[s];
-                    ltr::ltr_commit(a.ltr_slots, a.ltr_state[s], t.final_action != ACT_NONE,
-                                    t.final_action == ACT_I && t.idr_on_intra, t.frame_num, t.num_rows * a.mb_w, s, s + 1,
-                                    a.ltr_task);
-                }
+            if (a.ltr_cfg.slots)
+                for (int s = tid; s < ns; s += 256)   // every stripe's stream
+                    ltr_stream_commit(a.ltr_cfg, a.ltr_state[s], a.tasks, a.ltr_task, s, s + 1, a.mb_w, a.mb_w * a.mb_h, false,
+                                      false);
             for (int s = tid; s < ns; s += 256)
                 commit_stripe(st[s], a.tasks[s].final_action, a.plan_cfg.num_refs, a.tasks[s].idr_on_intra != 0);
         }
@@ -988,8 +979,7 @@ __global__ __launch_bounds__(256) void k_ltr_match(FrameArgs a) {
         a.ltr_cnt[2 * s] = nd;
         a.ltr_cnt[2 * s + 1] = gate;
     }
-    // AV1 (ltr_unit): the tile row is the unit, so the slices the plan left clean are compared too
-    if (!gate || (t.action != ACT_P && !a.ltr_unit) || band >= t.num_rows || (c > 0 && !((valid >> (c - 1)) & 1))) return;
+    if (!gate || !ltr_slice_compared(a.ltr_cfg, t) || band >= t.num_rows || (c > 0 && !((valid >> (c - 1)) & 1))) return;
     const uint8_t* ref = c ? a.ltr.y + (size_t)(c - 1) * a.ltr_ny : a.ref.y;
     const size_t o = (size_t)(t.first_row + band) * 16 * a.stride_y;
     const uint4* q = reinterpret_cast<const uint4*>(a.src.y + o);
@@ -1011,15 +1001,15 @@ __global__ __launch_bounds__(256) void k_ltr_match(FrameArgs a) {
             (uint32_t)red[0] + (uint32_t)red[1] + (uint32_t)red[2] + (uint32_t)red[3];
 }
 
-// k_ltr_decide (one workgroup): the MB-row sums of the gated slices, then ltr_decide with one
-// lane per stream into LtrTask / LtrState; a slice that chose a slot codes with two references.
+// k_ltr_decide (one workgroup): the MB-row sums of the gated slices, then ltr_stream_decide
+// (h264_encoder.h, the CPU back end's) with one lane per stream into LtrTask / LtrState.
 __global__ __launch_bounds__(256) void k_ltr_decide(FrameArgs a) {
     const int ns = a.num_slices, tid = threadIdx.x;
     for (int i = tid; i < ns * ltr::kLtrSadCols; i += 256) {
         const int s = i / ltr::kLtrSadCols, c = i - s * ltr::kLtrSadCols;
         const int valid = a.ltr_state[a.fullframe ? ns : s].valid;
         uint32_t sum = 0;
-        if (a.ltr_cnt[2 * s + 1] && (a.tasks[s].action == ACT_P || a.ltr_unit) && c <= a.ltr_slots && (c == 0 || ((valid >> (c - 1)) & 1)))
+        if (a.ltr_cnt[2 * s + 1] && ltr_slice_compared(a.ltr_cfg, a.tasks[s]) && c <= a.ltr_cfg.slots && (c == 0 || ((valid >> (c - 1)) & 1)))
             for (int b = 0; b < a.tasks[s].num_rows; b++) sum += a.ltr_part[(size_t)i * a.rows_per_slice + b];
         a.ltr_sad[i] = sum;
     }
@@ -1027,25 +1017,8 @@ __global__ __launch_bounds__(256) void k_ltr_decide(FrameArgs a) {
     const int streams = a.fullframe ? 1 : ns;
     for (int k = tid; k < streams; k += 256) {
         const int s0 = a.fullframe ? 0 : k, s1 = a.fullframe ? ns : k + 1;
-        bool key = false, anyp = false;
-        int rows = 0;
-        for (int s = s0; s < s1; s++) {
-            key |= a.tasks[s].action == ACT_I;
-            anyp |= a.tasks[s].action == ACT_P;
-            rows += a.tasks[s].num_rows;
-        }
-        if (a.ltr_excl && !a.ltr_unit) ltr::ltr_expire(a.ltr_slots, a.ltr_state[ns], a.tasks[s0].frame_num, a.ltr_max_age);
-        const bool planned_p = anyp && !key;
-        if (a.ltr_unit && a.ltr_cnt[2 * s0 + 1])   // AV1: one sum per tile row, so its slices match the same slot
-            ltr::ltr_sum_units(a.ltr_slots, a.ltr_state[ns].valid, s0, s1, a.ltr_unit, a.ltr_sad);
-        ltr::ltr_decide(a.ltr_slots, a.ltr_state[a.fullframe ? ns : k], a.ltr_cnt[2 * s0], rows * a.mb_w, planned_p,
-                        a.tasks[s0].frame_num, kFrameNumMask, s0, s1,
-                        [&](int s) { return a.ltr_unit ? planned_p : a.tasks[s].action == ACT_P; }, a.ltr_sad,
-                        a.ltr_task);
-        if (a.ltr_unit)   // one slot per frame; ref1_mbs of every slice, clean ones included
-            ltr::ltr_av1_reduce(a.ltr_slots, s0, s1, [&](int s) { return a.tasks[s].num_rows * a.mb_w; }, a.ltr_task);
-        for (int s = s0; s < s1; s++)
-            if (a.ltr_task[s].slot >= 0 && !a.ltr_excl) a.tasks[s].num_refs = 2;   // [previous picture, the slot]
+        ltr_stream_decide(a.ltr_cfg, a.ltr_state[a.fullframe ? ns : k], a.tasks, s0, s1, a.ltr_cnt[2 * s0], a.mb_w,
+                          a.ltr_cnt[2 * s0 + 1] != 0, a.ltr_sad, a.ltr_task);
     }
 }
 
@@ -1068,7 +1041,7 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
             ref1 += r.ref == 1;
         }
     }
-    if (a.ltr_slots) {
+    if (a.ltr_cfg.slots) {
         for (int o = 32; o > 0; o >>= 1) ref1 += __shfl_down(ref1, o);
         if (lane_id() == 0) red1[threadIdx.x >> 6] = ref1;
     }
@@ -1085,12 +1058,9 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
         const long long ts = red[0][0] + red[0][1] + red[0][2] + red[0][3];
         const long long td = red[1][0] + red[1][1] + red[1][2] + red[1][3];
         t.final_action = (p && ts > td) ? ACT_I : t.action;
-        if (a.ltr_unit) {
-            // AV1: set with the decision (ltr_av1_reduce): clean slices of a matched tile row count too
-        } else if (a.ltr_excl)
-            a.ltr_task[s].ref1_mbs = ltr::ltr_exclusive_mbs(a.ltr_task[s], planned_p && t.final_action == ACT_P, t.num_rows * a.mb_w);
-        else if (a.ltr_slots)
-            a.ltr_task[s].ref1_mbs = (planned_p && t.final_action == ACT_P) ? red1[0] + red1[1] + red1[2] + red1[3] : 0;
+        if (a.ltr_cfg.slots)
+            a.ltr_task[s].ref1_mbs = ltr::ltr_ref1_mbs(a.ltr_cfg, a.ltr_task[s], planned_p && t.final_action == ACT_P,
+                                                       t.num_rows * a.mb_w, red1[0] + red1[1] + red1[2] + red1[3]);
         a.rc_slice[2 * s] = ts;       // K10 complexity (k_rc_qp)
         a.rc_slice[2 * s + 1] = td;
         a.tasks_host[s] = t;  // final decision back to the host (host-mapped)
@@ -3142,12 +3112,12 @@ __global__ __launch_bounds__(kPackThreads) void k_slice_pack(FrameArgs a) {
             h.slice_qp = task.qp;
             h.deblock = slice_deblock(a.deblock, task);
             h.num_refs = intra ? 1 : task.num_refs;
-            if (a.ltr_slots) {   // long-term cache: list modification / marking, as the CPU writer
+            if (a.ltr_cfg.slots) {   // long-term cache: list modification / marking, as the CPU writer
                 const ltr::LtrTask L = a.ltr_task[s];
                 if (fin == ACT_P) h.lt_ref = L.slot;
                 if (!idr && L.store_slot >= 0) {
                     h.lt_store = L.store_slot;
-                    h.lt_max_idx = a.ltr_slots;
+                    h.lt_max_idx = a.ltr_cfg.slots;
                     h.st_drop = L.mmco1;
                 }
             }
@@ -3396,7 +3366,7 @@ __global__ __launch_bounds__(256) void k_commit(FrameArgs a, int account) {
     // sliding-window DPB: the current reference becomes reference 1 (a skip-all picture
     // is a reference too); the same thread then overwrites ref with rec below
     if (a.num_refs > 1) copy(a.ref, a.ref1);
-    if (a.ltr_slots) {   // long-term store: the previous picture's rows go to the slot before rec replaces them
+    if (a.ltr_cfg.slots) {   // long-term store: the previous picture's rows go to the slot before rec replaces them
         const int j = a.ltr_task[s].store_slot;
         if (j >= 0) copy(a.ref, Planes{a.ltr.y + (size_t)j * a.ltr_ny, a.ltr.u + (size_t)j * a.ltr_nc,
                                        a.ltr.v + (size_t)j * a.ltr_nc});
@@ -3722,8 +3692,8 @@ void launch_convert_damage(const FrameArgs& a, hipStream_t s) {
 void launch_frontend(const FrameArgs& a, hipStream_t s) {
     int nmb = a.mb_w * a.mb_h;
     hipLaunchKernelGGL(k_plan, dim3(1), dim3(256), 0, s, a);
-    if (a.ltr_slots) {   // long-term cache: these two nodes exist only with EncoderConfig::ltr_slots > 0
-        hipLaunchKernelGGL(k_ltr_match, dim3(a.rows_per_slice, 1 + a.ltr_slots, a.num_slices), dim3(256), 0, s, a);
+    if (a.ltr_cfg.slots) {   // long-term cache: these two nodes exist only with EncoderConfig::ltr_slots > 0
+        hipLaunchKernelGGL(k_ltr_match, dim3(a.rows_per_slice, 1 + a.ltr_cfg.slots, a.num_slices), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_ltr_decide, dim3(1), dim3(256), 0, s, a);
     }
     if (a.me_full) hipLaunchKernelGGL(k_me, dim3(a.mb_h * ((a.mb_w + kFsGroup - 1) / kFsGroup)), dim3(256), 0, s, a);

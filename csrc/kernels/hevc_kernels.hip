@@ -2038,7 +2038,7 @@ __global__ __launch_bounds__(64) void k_hevc_hdr(HevcArgs A) {
     // long-term cache: the RPS every slice carries (state after this picture's expiry, before
     // its commit in the next k_plan), list 0 of a matched P slice
     auto lt_fields = [&](SliceHeader& h, bool p_slice) {
-        if (!f.ltr_slots) return;
+        if (!f.ltr_cfg.slots) return;
         const ltr::LtrState& ls = f.ltr_state[f.num_slices];
         h.lt_present = 1;
         h.lt_valid = ls.valid;

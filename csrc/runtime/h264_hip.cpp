@@ -353,7 +353,7 @@ class HipBackend : public EncoderBackend {
         return (int)packets_.size();
     }
 
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(g_, args_.ltr_slots); }
+    int64_t state_bytes() override { return (int64_t)h264::state_bytes(g_, args_.ltr_cfg.slots); }
 
     // Copies `n` bytes between this encoder's device buffer and a caller buffer
     // that is device (on_device) or host memory.
@@ -373,7 +373,7 @@ class HipBackend : public EncoderBackend {
                      h_key_seq_[2] > 0 ? h_key_seq_[2] : cfg_.paint_qp, h);
         const std::vector<StripeState> st = committed_stripes(pc);
         const std::vector<ltr::LtrState> ls = committed_ltr_state(pc);
-        state_sections(g_, args_.ltr_slots, [&](const StateSection& s) {
+        state_sections(g_, args_.ltr_cfg.slots, [&](const StateSection& s) {
             uint8_t* o = static_cast<uint8_t*>(dst) + s.off;
             const void* host = s.kind == ST_HEADER ? (const void*)&h
                                : s.kind == ST_STRIPES ? (const void*)st.data()
@@ -400,7 +400,7 @@ class HipBackend : public EncoderBackend {
             return -1;
         }
         RcState rc;   // alive until the copies below are done
-        state_sections(g_, args_.ltr_slots, [&](const StateSection& s) {
+        state_sections(g_, args_.ltr_cfg.slots, [&](const StateSection& s) {
             const uint8_t* i = static_cast<const uint8_t*>(src) + s.off;
             if (s.kind == ST_RC) {   // K10 state; its set_rate() counter is this encoder's, so k_rc_qp keeps it
                 to_host(&rc, i, sizeof(rc));
@@ -465,7 +465,7 @@ class HipBackend : public EncoderBackend {
         if (s == "tasks")   // of the last finished frame
             return from_host(slot_[(finished_ + 1) & 1].tasks.host, g_.num_slices * sizeof(SliceTask));
         if (s == "av1_geo" && cfg_.codec == 2) return from_host(&av1_geo_, sizeof(av1_geo_));
-        if (s == "ltr_state" && args_.ltr_slots) {
+        if (s == "ltr_state" && args_.ltr_cfg.slots) {
             const std::vector<ltr::LtrState> ls = committed_ltr_state(pending_commit());
             return from_host(ls.data(), ls.size() * sizeof(ltr::LtrState));
         }
@@ -478,7 +478,7 @@ class HipBackend : public EncoderBackend {
         else if (s == "src_u") { p = last_src.u; n = nc; }
         else if (s == "src_v") { p = last_src.v; n = nc; }
         else if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
-                 s[3] < '0' + args_.ltr_slots) { p = args_.ltr.y + (size_t)(s[3] - '0') * ny; n = ny; }
+                 s[3] < '0' + args_.ltr_cfg.slots) { p = args_.ltr.y + (size_t)(s[3] - '0') * ny; n = ny; }
         else
             for (const DebugEntry& e : debug_)
                 if (s == e.name && (e.codec < 0 || e.codec == cfg_.codec)) { p = e.dev; n = e.bytes; break; }
@@ -529,7 +529,7 @@ class HipBackend : public EncoderBackend {
     }
     // Long-term cache state as the CPU back end holds it after a frame (empty: cache off).
     std::vector<ltr::LtrState> committed_ltr_state(const PendingCommit& pc) {
-        const int ns = g_.num_slices, slots = args_.ltr_slots;
+        const int ns = g_.num_slices, slots = args_.ltr_cfg.slots;
         std::vector<ltr::LtrState> ls(slots ? ns + 1 : 0);
         if (!slots) return ls;
         std::vector<ltr::LtrTask> lt(ns);
@@ -537,17 +537,10 @@ class HipBackend : public EncoderBackend {
         copy_now(lt.data(), args_.ltr_task, sizeof(ltr::LtrTask) * ns);
         const std::vector<SliceTask>& tasks = pc.tasks;
         if (!pc.commit) return ls;
-        if (args_.ltr_unit)
-            ltr::ltr_commit_av1(slots, ls[ns], pc.idr, g_.num_mbs(), 0, ns, lt.data());
-        else if (args_.ltr_excl)
-            ltr::ltr_commit_rps(slots, ls[ns], pc.idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
-        else if (cfg_.fullframe)
-            ltr::ltr_commit(slots, ls[ns], true, pc.idr, tasks[0].frame_num, g_.num_mbs(), 0, ns, lt.data());
-        else
-            for (int s = 0; s < ns; s++)
-                ltr::ltr_commit(slots, ls[s], tasks[s].final_action != ACT_NONE,
-                                tasks[s].final_action == ACT_I && tasks[s].idr_on_intra, tasks[s].frame_num,
-                                tasks[s].num_rows * g_.mb_w, s, s + 1, lt.data());
+        const bool ff = cfg_.fullframe != 0;
+        for (int s = 0; s < (ff ? 1 : ns); s++)   // one stream: the picture, or every stripe
+            ltr_stream_commit(args_.ltr_cfg, ls[ff ? ns : s], tasks.data(), lt.data(), s, ff ? ns : s + 1, g_.mb_w,
+                              g_.num_mbs(), ff, pc.idr);
         return ls;
     }
 
@@ -656,17 +649,14 @@ class HipBackend : public EncoderBackend {
         a.ref = make_planes();
         a.ref1 = make_planes();
         a.rec = make_planes();
-        a.ltr_slots = ltr_slots_of(cfg_);
-        a.ltr_excl = a.ltr_slots > 0 && cfg_.codec >= 1;   // HEVC, AV1: one reference per slice (ltr.h exclusive mode)
-        a.ltr_unit = ltr_unit_slices_of(cfg_);             // AV1: the tile row decides (ltr.h buffer map)
-        a.ltr_max_age = ltr_max_age_env();
-        if (a.ltr_slots) {   // long-term cache (codec/ltr.h): slot plane sets, stream states, per-frame decisions
+        a.ltr_cfg = ltr_config_of(cfg_);
+        if (a.ltr_cfg.slots) {   // long-term cache (codec/ltr.h): slot plane sets, stream states, per-frame decisions
             const size_t ny = (size_t)g_.stride_y * g_.plane_h_y, nc = (size_t)g_.stride_c * g_.plane_h_c;
             a.ltr_ny = ny;
             a.ltr_nc = nc;
-            a.ltr.y = mem_.dmalloc<uint8_t>(ny * a.ltr_slots);
-            a.ltr.u = mem_.dmalloc<uint8_t>(nc * a.ltr_slots);
-            a.ltr.v = mem_.dmalloc<uint8_t>(nc * a.ltr_slots);
+            a.ltr.y = mem_.dmalloc<uint8_t>(ny * a.ltr_cfg.slots);
+            a.ltr.u = mem_.dmalloc<uint8_t>(nc * a.ltr_cfg.slots);
+            a.ltr.v = mem_.dmalloc<uint8_t>(nc * a.ltr_cfg.slots);
             ltr::LtrState z;
             ltr::ltr_state_reset(z);
             std::vector<ltr::LtrState> init(ns + 1, z);
@@ -1013,7 +1003,7 @@ class HipBackend : public EncoderBackend {
         fp.key = f.av1_frame.host[0];
         fp.qidx = f.av1_frame.host[1];
         fp.lf_level = f.av1_frame.host[2];
-        if (args_.ltr_unit) {   // long-term cache: the reference buffers k_av1_setup chose (ltr.h buffer map)
+        if (args_.ltr_cfg.mode == ltr::LTR_BUFMAP) {   // long-term cache: the reference buffers k_av1_setup chose (ltr.h buffer map)
             fp.refresh = f.av1_frame.host[3];
             fp.last_buf = f.av1_frame.host[4];
             fp.last2_buf = f.av1_frame.host[5];

@@ -59,7 +59,7 @@ DebugBuf ltr_debug(h264::CpuH264Encoder& e, const std::string& s) {
     if (s == "ltr_state") return bytes_of(e.ltr_state);
     if (s == "ltr_task") return bytes_of(e.ltr_task);
     if (s.size() == 6 && s.compare(0, 3, "ltr") == 0 && s.compare(4, 2, "_y") == 0 && s[3] >= '0' &&
-        s[3] < '0' + e.ltr_slots_) return bytes_of(e.ltr_planes[s[3] - '0'][0]);
+        s[3] < '0' + e.ltr_cfg.slots) return bytes_of(e.ltr_planes[s[3] - '0'][0]);
     return {nullptr, -1};
 }
 DebugBuf codec_debug(h264::CpuH264Encoder& e, const std::string& s) {
@@ -148,7 +148,7 @@ class CpuBackend : public EncoderBackend {
         return b.second;
     }
 
-    int64_t state_bytes() override { return (int64_t)h264::state_bytes(fe().g, fe().ltr_slots_); }
+    int64_t state_bytes() override { return (int64_t)h264::state_bytes(fe().g, fe().ltr_cfg.slots); }
     int export_state(void* dst, int on_device) override {
         if (on_device) return -1;
         h264::cpu_export_state(fe(), dst);

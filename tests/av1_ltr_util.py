@@ -8,41 +8,14 @@ import numpy as np
 
 from selkies_gstreamer_amd.models.av1 import dav1d
 from selkies_gstreamer_amd.ops.native import Av1Encoder
-from tests.ltr_util import H, STRIPE, W, contents, sequence  # noqa: F401  (re-exported)
+from tests.ltr_util import (H, STRIPE, W, contents, ltr_slots_of_tasks, ltr_tasks, ltr_valid, make_enc,  # noqa: F401
+                            ref_planes, sequence)                                                    # (re-exported)
 
-LTR_TASK_WORDS = 8     # sizeof(LtrTask) / 4: slot, store_slot, mmco1, flags, ref1_mbs, pad[3]
-LTR_STATE_WORDS = 24   # sizeof(LtrState) / 4: quiet_run, cur_slot, clock, valid, stamp[8], n_st, st_fn[9], pad[2]
 BLK_REF = 11           # BlkInfo's last byte: the block's reference, 0 = LAST, 1 = LAST2
 
 
 def av1_enc(slots=None, w=W, h=H, backend="cpu", **kw):
-    kw = dict(dict(stripe_height=STRIPE, qp=24, use_paint_over=False), **kw)
-    if slots is not None:
-        kw["ltr_slots"] = slots
-    return Av1Encoder(w, h, backend=backend, **kw)
-
-
-def ref_planes(enc, w, h):
-    sy, ph = ((w + 15) // 16) * 16, ((h + 15) // 16) * 16
-    ry = enc.debug_buffer("ref_y").reshape(ph, sy)[:h, :w]
-    ru = enc.debug_buffer("ref_u").reshape(ph // 2, sy // 2)[:h // 2, :w // 2]
-    rv = enc.debug_buffer("ref_v").reshape(ph // 2, sy // 2)[:h // 2, :w // 2]
-    return ry, ru, rv
-
-
-def ltr_tasks(enc) -> np.ndarray:
-    """[slices][LTR_TASK_WORDS] of the frame just coded."""
-    return enc.debug_buffer("ltr_task", np.int32).reshape(-1, LTR_TASK_WORDS)
-
-
-def ltr_slots_of_tasks(enc) -> list:
-    """LtrTask::slot of every slice of the frame just coded."""
-    return ltr_tasks(enc)[:, 0].tolist()
-
-
-def ltr_valid(enc) -> int:
-    """LtrState::valid of the picture's stream (the last state)."""
-    return int(enc.debug_buffer("ltr_state", np.int32).reshape(-1, LTR_STATE_WORDS)[-1, 3])
+    return make_enc(Av1Encoder, slots, w, h, backend, **kw)
 
 
 def blk_refs(enc, w, h) -> np.ndarray:
@@ -131,7 +104,7 @@ class CheckedAv1:
         assert out["refs"]["key"] == out["key"]
         if self.model is not None:
             lt = ltr_tasks(self.enc)
-            out["slots"], out["store"] = lt[:, 0].tolist(), int(lt[0, 1])
+            out["slots"], out["store"] = lt["slot"].tolist(), int(lt["store_slot"][0])
             out["valid"] = ltr_valid(self.enc)
             used = sorted({s for s in out["slots"] if s >= 0})
             assert len(used) <= 1, f"frame {self.t - 1}: more than one cached picture in a frame: {used}"

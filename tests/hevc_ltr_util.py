@@ -9,40 +9,12 @@ import numpy as np
 
 from selkies_gstreamer_amd.models.hevc.decoder import HevcDecoder
 from selkies_gstreamer_amd.ops.native import HevcEncoder
-from tests.ltr_util import H, STRIPE, W, contents, sequence  # noqa: F401  (re-exported)
-
-LTR_TASK_WORDS = 8     # sizeof(LtrTask) / 4: slot, store_slot, mmco1, flags, ref1_mbs, pad[3]
-LTR_STATE_WORDS = 24   # sizeof(LtrState) / 4: quiet_run, cur_slot, clock, valid, stamp[8], n_st, st_fn[9], pad[2]
+from tests.ltr_util import (H, STRIPE, W, contents, final_actions, ltr_slots_of_tasks, ltr_valid,  # noqa: F401
+                            make_enc, ref_planes, sequence)                                       # (re-exported)
 
 
 def hevc_enc(slots=None, w=W, h=H, backend="cpu", **kw):
-    kw = dict(dict(stripe_height=STRIPE, qp=24, use_paint_over=False), **kw)
-    if slots is not None:
-        kw["ltr_slots"] = slots
-    return HevcEncoder(w, h, backend=backend, **kw)
-
-
-def ref_planes(enc, w, h):
-    sy, ph = ((w + 15) // 16) * 16, ((h + 15) // 16) * 16
-    ry = enc.debug_buffer("ref_y").reshape(ph, sy)[:h, :w]
-    ru = enc.debug_buffer("ref_u").reshape(ph // 2, sy // 2)[:h // 2, :w // 2]
-    rv = enc.debug_buffer("ref_v").reshape(ph // 2, sy // 2)[:h // 2, :w // 2]
-    return ry, ru, rv
-
-
-def ltr_slots_of_tasks(enc) -> list:
-    """LtrTask::slot of every slice of the frame just coded."""
-    return enc.debug_buffer("ltr_task", np.int32).reshape(-1, LTR_TASK_WORDS)[:, 0].tolist()
-
-
-def ltr_valid(enc) -> int:
-    """LtrState::valid of the picture's stream (the last state)."""
-    return int(enc.debug_buffer("ltr_state", np.int32).reshape(-1, LTR_STATE_WORDS)[-1, 3])
-
-
-def final_actions(enc) -> list:
-    """SliceTask::final_action of every slice of the frame just coded (1 = P, 2 = I, 3 = skip-all)."""
-    return enc.debug_buffer("tasks", np.int32).reshape(-1, 12)[:, 10].tolist()
+    return make_enc(HevcEncoder, slots, w, h, backend, **kw)
 
 
 class CheckedHevc:

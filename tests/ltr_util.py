@@ -1,11 +1,12 @@
-"""Shared helpers of the long-term reference cache tests (test_h264_ltr.py, test_h264_ltr_gpu.py):
-window-switch content, and an encode loop that decodes every packet and compares the decoder's
-picture with the encoder's reference planes."""
+"""Shared helpers of the long-term reference cache tests of all three codecs: window-switch content,
+the encoder factory's defaults, readers of the cache's debug buffers, and the H.264 encode loop that
+decodes every packet and compares the decoder's picture with the encoder's reference planes
+(hevc_ltr_util.py and av1_ltr_util.py hold their codec's loop)."""
 from __future__ import annotations
 
 import numpy as np
 
-from selkies_gstreamer_amd.ops.native import ME_DTYPE
+from selkies_gstreamer_amd.ops.native import LTR_STATE_DTYPE, LTR_TASK_DTYPE, ME_DTYPE, TASK_DTYPE
 from tests.h264_util import StripeDecoder, psnr, synthetic_frames
 
 W, H = 208, 112          # 13 x 7 MBs; with stripe_height 32: four stripes, the last of one MB row
@@ -39,6 +40,43 @@ def sequence(spec: str, w: int = W, h: int = H):
             t += 1
 
 
+def make_enc(cls, slots=None, w=W, h=H, backend="cpu", **kw):
+    """An encoder of class `cls` with the LTR tests' defaults; slots None: ltr_slots left unset."""
+    kw = dict(dict(stripe_height=STRIPE, qp=24, use_paint_over=False), **kw)
+    if slots is not None:
+        kw["ltr_slots"] = slots
+    return cls(w, h, backend=backend, **kw)
+
+
+def ref_planes(enc, w, h):
+    """The encoder's reference picture, cropped to w x h: (Y, U, V)."""
+    sy, ph = ((w + 15) // 16) * 16, ((h + 15) // 16) * 16
+    ry = enc.debug_buffer("ref_y").reshape(ph, sy)[:h, :w]
+    ru = enc.debug_buffer("ref_u").reshape(ph // 2, sy // 2)[:h // 2, :w // 2]
+    rv = enc.debug_buffer("ref_v").reshape(ph // 2, sy // 2)[:h // 2, :w // 2]
+    return ry, ru, rv
+
+
+def ltr_tasks(enc) -> np.ndarray:
+    """LtrTask of every slice of the frame just coded."""
+    return enc.debug_buffer("ltr_task", LTR_TASK_DTYPE)
+
+
+def ltr_slots_of_tasks(enc) -> list:
+    """LtrTask::slot of every slice of the frame just coded."""
+    return ltr_tasks(enc)["slot"].tolist()
+
+
+def ltr_valid(enc) -> int:
+    """LtrState::valid of the picture's stream (the last state)."""
+    return int(enc.debug_buffer("ltr_state", LTR_STATE_DTYPE)["valid"][-1])
+
+
+def final_actions(enc) -> list:
+    """SliceTask::final_action of every slice of the frame just coded (1 = P, 2 = I, 3 = skip-all)."""
+    return enc.debug_buffer("tasks", TASK_DTYPE)["final_action"].tolist()
+
+
 class Checked:
     """An encoder plus its decoders: every packet must decode, and the decoded picture must equal
     the encoder's reference planes."""
@@ -53,17 +91,14 @@ class Checked:
         self.t += 1
         for p in pk:
             self.dec.feed(p.data)
-        sy = ((self.w + 15) // 16) * 16
-        ph = ((self.h + 15) // 16) * 16
-        ry = self.enc.debug_buffer("ref_y").reshape(ph, sy)[:self.h, :self.w]
-        ru = self.enc.debug_buffer("ref_u").reshape(ph // 2, sy // 2)[:self.h // 2, :self.w // 2]
-        rv = self.enc.debug_buffer("ref_v").reshape(ph // 2, sy // 2)[:self.h // 2, :self.w // 2]
+        ry, ru, rv = ref_planes(self.enc, self.w, self.h)
         assert np.array_equal(self.dec.Y, ry), "decoder luma differs from the encoder's reference"
         assert np.array_equal(self.dec.U, ru) and np.array_equal(self.dec.V, rv), "decoder chroma differs"
         me = self.enc.debug_buffer("me", ME_DTYPE)
         out = {"bytes": sum(len(p.data) for p in pk), "key": any(p.key for p in pk), "ref1": int((me["ref"] == 1).sum()),
                "packets": [(p.y, p.key, p.data) for p in pk]}
         if src_psnr:
+            sy, ph = ((self.w + 15) // 16) * 16, ((self.h + 15) // 16) * 16
             sy_ = self.enc.debug_buffer("src_y").reshape(ph, sy)[:self.h, :self.w]
             out["psnr"] = psnr(sy_, ry)
         return out

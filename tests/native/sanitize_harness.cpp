@@ -88,7 +88,7 @@ int main() {
             oa.clear();
             a.encode(f.data(), c.width * 4, (uint16_t)t, oa);
         }
-        std::vector<uint8_t> blob(sk::h264::state_bytes(a.g, a.ltr_slots_));
+        std::vector<uint8_t> blob(sk::h264::state_bytes(a.g, a.ltr_cfg.slots));
         sk::h264::cpu_export_state(a, blob.data());
         bool same = sk::h264::cpu_import_state(b, blob.data());
         fill(f, c.width, c.height, 2, 0);
