@@ -885,6 +885,28 @@ __global__ __launch_bounds__(256) void k_me(FrameArgs a) {
                  MeWin{win_s + 4 * w, kFsWinWords, search ? kFsR : -1, 0, 0, 0x80808080u});
 }
 
+// K10 set_rate() from the host (key: the snapshot; [3] rc mode, [4] kbps, [5] change counter):
+// re-initialises the controller and keeps the model if the mode stays, as Controller::set_rate.
+// In k_plan, ahead of everything that reads the controller in this frame: the motion search
+// prices its vectors by it (rc_me_qp), and the CPU back end has the new state by then. (In
+// k_rc_qp, behind the search, the first frame after a change from CBR or CRF to another mode
+// searched at the old mode's last QP and coded other vectors than the CPU back end.)
+__device__ void rc_set_rate(const FrameArgs& a, const int* key, RcState& rc) {
+    const int mode = key[3], kbps = key[4];
+    const RcState old = rc;
+    rc_init(rc, mode, key[1] > 0 ? key[1] : a.plan_cfg.qp, kbps, (float)a.rc_fps, a.W * a.H, old.vbv_ms, old.codec);
+    if (old.mode == mode) {
+        for (int k = 0; k < 2; k++) {
+            rc.last_qp[k] = old.last_qp[k];
+            rc.last_qpf[k] = old.last_qpf[k];
+            rc.last_bits[k] = old.last_bits[k];
+            rc.last_cplx[k] = old.last_cplx[k];
+        }
+        rc.cplx_ema = old.cplx_ema;
+    }
+    rc.seq = key[5];
+}
+
 // Frame controller on the GPU (one workgroup): commits the previous frame's
 // final slice decisions, applies host keyframe requests (host-mapped counter)
 // and plans this frame from the stripe dirty flags of k_convert_damage — the
@@ -914,8 +936,13 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
     // host overrides: the device copy of the host-mapped snapshot that the damage kernel
     // left (host_words_store), which k_rc_qp reads too
     __shared__ int hk[6];
+    __shared__ int rc_mode;
     if (tid < 6) hk[tid] = a.key_dev[tid];
     __syncthreads();
+    if (tid == 0) {
+        if (hk[5] != a.rc->seq) rc_set_rate(a, hk, *a.rc);
+        rc_mode = a.rc->mode;
+    }
     const int kq = hk[0];
     const bool key = kq != a.plan_ctl[0];
     __syncthreads();
@@ -929,10 +956,8 @@ __global__ __launch_bounds__(256) void k_plan(FrameArgs a) {
     const int po = hk[2];
     if (qo > 0) pc.qp = qo;
     if (po > 0) pc.paint_qp = po;
-    {   // K10 CBR: no paint-over refresh (the budget codes every slice at the frame QP anyway)
-        const int mode = hk[5] != a.rc->seq ? hk[3] : a.rc->mode;
-        if (mode == RC_CBR) pc.use_paint_over = 0;
-    }
+    // K10 CBR: no paint-over refresh (the budget codes every slice at the frame QP anyway)
+    if (rc_mode == RC_CBR) pc.use_paint_over = 0;
     for (int s = tid; s < ns; s += 256) {
         st[s].subpel_prev = st[s].subpel_hits;   // adaptive refinement gate (h264_frame.h subpel_gate)
         st[s].subpel_hits = 0;
@@ -1068,28 +1093,12 @@ __global__ __launch_bounds__(256) void k_decide(FrameArgs a) {
 }
 
 // K10: frame QP from the complexity sums (same rc_apply as the CPU controller).
-// Host overrides: key_seq_host[1] qp, [3] rc mode, [4] kbps, [5] change counter.
+// Host override: key_seq_host[1] qp (a set_rate() was applied by k_plan, rc_set_rate).
 // `key`: the device copy of the host snapshot; `sums`: rc_slice ([slice][2]).
 __device__ void rc_qp_serial(const FrameArgs& a, const int* key, RcState& rc, SliceTask* tasks, const long long* sums) {
-    const int seq = key[5];
     int plan_qp = a.plan_cfg.qp;
     const int qo = key[1];
     if (qo > 0) plan_qp = qo;
-    if (seq != rc.seq) {   // set_rate() from the host: re-initialise, keep the model if the mode stays
-        const int mode = key[3];
-        const int kbps = key[4];
-        const RcState old = rc;
-        rc_init(rc, mode, plan_qp, kbps, (float)a.rc_fps, a.W * a.H, old.vbv_ms, old.codec);
-        if (old.mode == mode)
-            for (int k = 0; k < 2; k++) {
-                rc.last_qp[k] = old.last_qp[k];
-                rc.last_qpf[k] = old.last_qpf[k];
-                rc.last_bits[k] = old.last_bits[k];
-                rc.last_cplx[k] = old.last_cplx[k];
-            }
-        if (old.mode == mode) rc.cplx_ema = old.cplx_ema;
-        rc.seq = seq;
-    }
     rc.base_qp = plan_qp;
     rc_apply(rc, tasks, sums, sums + 1, a.num_slices, a.mb_w, plan_qp, 2);
 }

@@ -14,14 +14,20 @@ class EncoderBackend {
    public:
     virtual ~EncoderBackend() = default;
     virtual void request_keyframe() = 0;
+    // One frame, synchronously: returns the packet count of that frame. Refused (-1, nothing
+    // uploaded or coded) while a submitted / launched frame is uncollected: finish() hands out
+    // the oldest frame, so the call could only return another frame's packets or leave one behind.
     virtual int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) = 0;
     // Split form of encode(): submit() queues the frame (the caller keeps `bgrx`
-    // alive until finish()), finish() waits and returns the packet count. Several
-    // encoders can be submitted before any is finished (bands of one frame, or
-    // sessions driven from one thread). Default: synchronous; the packets of each
-    // submitted frame are queued, so two frames may be submitted before finish().
+    // alive until finish()), finish() waits and returns the packet count of the oldest
+    // frame in flight. Several encoders can be submitted before any is finished (bands of
+    // one frame, or sessions driven from one thread). Default: synchronous; the packets of
+    // each submitted frame are queued, so two frames may be submitted before finish().
     virtual int submit(const uint8_t* bgrx, int stride, uint16_t frame_id) {
-        if (encode(bgrx, stride, frame_id) < 0) return -1;
+        in_submit_ = true;
+        const int n = encode(bgrx, stride, frame_id);
+        in_submit_ = false;
+        if (n < 0) return -1;
         done_.push_back(std::move(packets_));
         packets_.clear();
         return 0;
@@ -52,7 +58,8 @@ class EncoderBackend {
     virtual int launch() { return 0; }
     // Planar 4:2:0 input (h264::YuvInput: fmt YUV_I420 / YUV_NV12, planes and strides)
     // instead of BGRx; on_device: the planes are device memory of this encoder's GPU.
-    // Encodes the frame like encode() and returns the packet count.
+    // Encodes the frame like encode() and returns the packet count; refused like encode()
+    // while a frame is in flight.
     virtual int encode_yuv(const h264::YuvInput& in, int on_device, uint16_t frame_id) {
         (void)in; (void)on_device; (void)frame_id;
         set_last_error("this encoder takes BGRx input only");
@@ -84,7 +91,15 @@ class EncoderBackend {
     std::vector<h264::EncodedPacket> packets_;
 
    protected:
+    // encode() / encode_yuv() of a back end on the default submit(): true, with the error set,
+    // when the call comes from outside while a submitted frame waits for its finish().
+    bool refuse_queued(const char* call) {
+        if (in_submit_ || done_.empty()) return false;
+        set_last_error(std::string(call) + ": a frame is in flight; finish() it first");
+        return true;
+    }
     std::deque<std::vector<h264::EncodedPacket>> done_;
+    bool in_submit_ = false;   // inside the default submit()
 };
 
 // Damage-driven upload: the union of row-range lists (pairs [y0, y1), any order, from

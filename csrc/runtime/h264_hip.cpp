@@ -77,6 +77,12 @@ class HipBackend : public EncoderBackend {
     }
     ~HipBackend() override {
         hipSetDevice(device_);
+        // a launched, uncollected frame may still replay the graphs and read the buffers freed
+        // below, and an overlapped upload may still write an input buffer
+        hipStreamSynchronize(stream_);
+        if (up_stream_) hipStreamSynchronize(up_stream_);
+        for (auto& f : slot_)   // an upload on the device's shared copy stream, which outlives this encoder
+            if (f.copied) hipEventSynchronize(f.copied);
         invalidate_graphs();
         mem_.free_all();
         for (auto& f : slot_)
@@ -96,7 +102,7 @@ class HipBackend : public EncoderBackend {
         if (qp > 0) __atomic_store_n(&h_key_seq_[1], qp, __ATOMIC_SEQ_CST);
         if (paint_qp > 0) __atomic_store_n(&h_key_seq_[2], paint_qp, __ATOMIC_SEQ_CST);
     }
-    // K10: picked up by k_rc_qp at the next frame (a change counter tells it apart).
+    // K10: picked up by k_plan at the next frame (a change counter tells it apart).
     void set_rate(int mode, int kbps) override {
         cfg_.rc_mode = mode;   // graphs re-captured with / without the CBR guard (launch)
         __atomic_store_n(&h_key_seq_[3], mode, __ATOMIC_SEQ_CST);
@@ -113,8 +119,17 @@ class HipBackend : public EncoderBackend {
         return k;
     }
 
+    // finish() returns the oldest frame in flight: with one uncollected, encode() and encode_yuv()
+    // would hand back that frame's packets and leave the new frame behind, so they are refused.
+    bool refuse_inflight(const char* call) {
+        if (inflight() <= 0) return false;
+        set_last_error(std::string(call) + ": a frame is in flight; finish() it first");
+        return true;
+    }
+
     int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
-        submit(bgrx, stride, frame_id);
+        if (refuse_inflight("encode()")) return -1;
+        if (submit(bgrx, stride, frame_id) < 0) return -1;
         return finish();
     }
 
@@ -165,6 +180,7 @@ class HipBackend : public EncoderBackend {
     // staging buffer in the packed layout k_yuv_damage reads; the graphs are captured
     // per input kind (BGRx / I420 / NV12).
     int encode_yuv(const YuvInput& in, int on_device, uint16_t frame_id) override {
+        if (refuse_inflight("encode_yuv()")) return -1;
         if (upload_yuv(in, on_device, frame_id) < 0) return -1;
         if (launch() < 0) return -1;
         return finish();
@@ -402,11 +418,14 @@ class HipBackend : public EncoderBackend {
         RcState rc;   // alive until the copies below are done
         state_sections(g_, args_.ltr_cfg.slots, [&](const StateSection& s) {
             const uint8_t* i = static_cast<const uint8_t*>(src) + s.off;
-            if (s.kind == ST_RC) {   // K10 state; its set_rate() counter is this encoder's, so k_rc_qp keeps it
+            if (s.kind == ST_RC) {   // K10 state; its set_rate() counter is this encoder's, so k_plan keeps it
                 to_host(&rc, i, sizeof(rc));
                 rc.seq = __atomic_load_n(&h_key_seq_[5], __ATOMIC_SEQ_CST);
                 dev_rc_mode_ = rc.mode;   // can_filter(): the device controller now runs in the imported mode
                 dev_rc_seq_ = rc.seq;
+                // launch(): graphs with the CBR guard exactly when the imported controller runs CBR (an
+                // encoder created in another mode captured them without it and never coded a frame again)
+                cfg_.rc_mode = rc.mode;
                 HIPCHECK(hipMemcpyAsync(args_.rc, &rc, sizeof(rc), hipMemcpyHostToDevice, stream_));
             } else if (s.kind != ST_HEADER) {
                 xfer(section_dev(s), i, s.bytes, false, on_device);
@@ -848,7 +867,7 @@ class HipBackend : public EncoderBackend {
     // Automatic (slices at QP >= kAutoDeblockQp): not when max_slice_qp, for the frame's
     // rate mode and QPs, stays below the threshold - every CQP / CRF session at the default
     // QPs. CBR reaches every QP and always takes the long graph. The rate mode is the device
-    // controller's at that frame: k_rc_qp takes the snapshot's mode when its set_rate()
+    // controller's at that frame: k_plan takes the snapshot's mode when its set_rate()
     // counter moved (as here), else keeps its own (initial, or imported with a state).
     bool can_filter(const int* snap) {
         if (!args_.deblock) return false;

@@ -50,6 +50,7 @@ class HipJpegBackend : public EncoderBackend {
     }
 
     int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
+        if (refuse_queued("encode()")) return -1;
         trace::Range frame_range("jpeg.frame");
         HIPCHECK(hipSetDevice(device_));
         packets_.clear();

@@ -123,11 +123,13 @@ class CpuBackend : public EncoderBackend {
         return 0;
     }
     int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
+        if (refuse_queued("encode()")) return -1;
         packets_.clear();
         enc_.encode(bgrx, stride, frame_id, packets_);
         return (int)packets_.size();
     }
     int encode_yuv(const h264::YuvInput& in, int on_device, uint16_t frame_id) override {
+        if (refuse_queued("encode_yuv()")) return -1;
         if (fe().scaled_) { set_last_error("planar input cannot be resampled"); return -1; }
         HostYuv h;
         if (h.load(in, on_device, fe().g.W, fe().g.H) < 0) return -1;
@@ -174,6 +176,7 @@ class CpuJpegBackend : public EncoderBackend {
     explicit CpuJpegBackend(const jpeg::JpegConfig& c) : enc_(c) {}
     void request_keyframe() override { enc_.request_keyframe(); }
     int encode(const uint8_t* bgrx, int stride, uint16_t frame_id) override {
+        if (refuse_queued("encode()")) return -1;
         packets_.clear();
         enc_.encode(bgrx, stride, frame_id, packets_);
         return (int)packets_.size();

@@ -410,7 +410,9 @@ class H264Encoder:
         lib().sk_h264_set_qp(self._h, int(qp), int(paint_qp))
 
     def encode(self, bgrx: np.ndarray, frame_id: int = 0) -> list[Packet]:
-        """bgrx: uint8 array (H, W, 4) or (H, stride) rows. Returns 0x04 stripe packets."""
+        """bgrx: uint8 array (H, W, 4) or (H, stride) rows. Returns 0x04 stripe packets of this
+        frame. Raises, with nothing uploaded or coded, while a submitted or launched frame is
+        uncollected: :meth:`finish` it first."""
         if bgrx.dtype != np.uint8:
             raise TypeError("bgrx must be uint8")
         if not bgrx.flags["C_CONTIGUOUS"]:
@@ -432,7 +434,8 @@ class H264Encoder:
         (y, u, v planes) or "nv12" (y plane, interleaved uv as ``u``). Planes are numpy
         uint8 arrays (host) or torch uint8 tensors on this encoder's GPU (device input,
         no host copy) or :class:`DevicePlane`. W x H luma, ((W+1)/2) x ((H+1)/2) chroma
-        (x2 wide for NV12 uv)."""
+        (x2 wide for NV12 uv). Synchronous like :meth:`encode`, and like it raises while a
+        submitted or launched frame is uncollected."""
         code = {"i420": 1, "nv12": 2}[fmt.lower()]
         planes = [y, u] + ([v] if code == 1 else [u])
         on_dev = int(isinstance(y, DevicePlane) or (hasattr(y, "data_ptr") and bool(getattr(y, "is_cuda", False))))
