@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from selkies_gstreamer_amd.ops.native import H264Encoder, HevcEncoder, hip_device_count
+from tests.frontend_model import composite
 from tests.h264_util import synthetic_frames
 
 
@@ -15,25 +16,6 @@ def premul(rng, h, w):
     img[..., 3] = np.where(rng.random((h, w)) < 0.2, 0, img[..., 3])   # fully transparent pixels
     img[..., :3] = (img[..., :3].astype(np.uint32) * img[..., 3:4] // 255).astype(np.uint8)
     return img
-
-
-def composite(frame, img, x, y, tile=None):
-    out = frame.copy()
-    H, W = frame.shape[:2]
-    h, w = img.shape[:2]
-    ys, xs = np.mgrid[0:H, 0:W]
-    dx, dy = xs - x, ys - y
-    ok = (dx >= 0) & (dy >= 0)
-    if tile:
-        dx, dy = dx % tile[0], dy % tile[1]
-    ok &= (dx < w) & (dy < h)
-    src = img[np.clip(dy, 0, h - 1), np.clip(dx, 0, w - 1)].astype(np.uint32)
-    a = src[..., 3:4]
-    d = out[..., :3].astype(np.uint32)
-    blended = ((src[..., :3] + (d * (255 - a) + 127) // 255) & 255).astype(np.uint8)
-    m = ok & (a[..., 0] > 0)
-    out[..., :3][m] = blended[m]
-    return out
 
 
 @pytest.mark.parametrize("place", ["inside", "clipped", "tiled"])

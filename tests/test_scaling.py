@@ -9,28 +9,8 @@ import numpy as np
 import pytest
 
 from selkies_gstreamer_amd.ops.native import H264Encoder
+from tests.frontend_model import np_scale
 from tests.h264_util import StripeDecoder, psnr, synthetic_frames
-
-
-def np_scale(src: np.ndarray, dw: int, dh: int) -> np.ndarray:
-    sh, sw = src.shape[:2]
-    stx, sty = (sw << 16) // dw, (sh << 16) // dh
-
-    def pos(d, step):
-        p = (((2 * d + 1).astype(np.int64) * step) >> 1) - 0x8000
-        return np.maximum(p, 0)
-    px, py = pos(np.arange(dw), stx), pos(np.arange(dh), sty)
-    x0 = np.minimum(px >> 16, sw - 1)
-    y0 = np.minimum(py >> 16, sh - 1)
-    x1, y1 = np.minimum(x0 + 1, sw - 1), np.minimum(y0 + 1, sh - 1)
-    wx, wy = ((px >> 8) & 255)[None, :, None], ((py >> 8) & 255)[:, None, None]
-    s = src.astype(np.int64)
-
-    def lerp(a, b, w):
-        return (a * (256 - w) + b * w + 128) >> 8
-    top = lerp(s[y0][:, x0], s[y0][:, x1], wx)
-    bot = lerp(s[y1][:, x0], s[y1][:, x1], wx)
-    return lerp(top, bot, wy).astype(np.uint8)
 
 
 def y709(bgrx):
