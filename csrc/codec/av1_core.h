@@ -15,12 +15,17 @@
 //   64x64 superblocks; blocks are square 8/16/32/64 (PARTITION_NONE or SPLIT only);
 //   TX_MODE_LARGEST (one transform per block, reduced_tx_set: DCT_DCT or IDTX, the
 //   screen-content identity transform, chosen per luma block); intra DC / V / H /
-//   SMOOTH(_V/_H) / PAETH / directional, luma palettes of 2..8 colours on key frames
+//   SMOOTH(_V/_H) / PAETH / directional, luma palettes of 2..8 colours
 //   (code_palette_mode_info / code_palette_tokens), no filter-intra / CfL / chroma
-//   palette / intraBC, intra edge filter off; one reference (LAST), single prediction, EIGHTTAP
-//   regular filter, quarter-pel vectors (allow_high_precision_mv = 0); no order
-//   hints (no temporal MVs, no skip mode); in-loop deblocking (av1_lf.h) and CDEF
-//   (av1_cdef.h) on, loop restoration off.
+//   palette / intraBC, intra edge filter off; one reference per block (LAST, or LAST2 for
+//   the cached picture of ltr.h), single prediction, EIGHTTAP regular filter, quarter-pel
+//   vectors (allow_high_precision_mv = 0); no order hints (no temporal MVs, no skip mode);
+//   in-loop deblocking (av1_lf.h) and CDEF (av1_cdef.h) on, loop restoration off.
+//   Key frames: every block intra, palettes where allow_screen_content_tools is set.
+//   Inter frames: every block inter, unless the session runs with av1_intra_inter: then the
+//   8x8 / 16x16 blocks whose inter coding left a residual may be intra blocks (is_inter = 0,
+//   intra_block_mode_info with the key frame's tools, palettes included: the frame sets
+//   allow_screen_content_tools), chosen by RD cost against the inter coding (kIntraInterBias2).
 #pragma once
 #include "sk_common.h"
 #include "av1_tables.h"
@@ -1092,11 +1097,17 @@ SK_HD CoefCtx coef_ctx(const FrameView& v, const TileRect& t, int plane, int x4,
 
 // ---------------------------------------------------------------------------------
 // Palette (screen content tools; §5.11.46 palette_mode_info, §5.11.49 palette_tokens,
-// §7.11.4 get_palette_cache / get_palette_color_context), luma only, on key frames.
+// §7.11.4 get_palette_cache / get_palette_color_context), luma only: intra blocks of key
+// frames and, with av1_intra_inter, of inter frames.
 // Encoder choice (av1_cpu.cpp intra_block = k_av1_intra_rec): a fully visible block
 // whose source luma takes 2..8 distinct values can be coded as that exact palette, with
 // no luma residual, when palette_rate2's cost is below the transform path's J.
 constexpr int kPalMax = 8;
+// av1_intra_inter (av1_cpu.cpp intra_trial = k_av1_inter_intra): an intra coding of a block of
+// an inter frame must beat the inter coding's J by the cost of this many half bits (tx_rd_cost's
+// rate unit): what is_inter = 0, y_mode, uv_mode and the palette flags cost above an inter
+// block's reference and mode symbols. Encoder choice (profiles/av1_intra_inter.md).
+constexpr int kIntraInterBias2 = 2 * 8;
 SK_HD int ceil_log2(int x) {
     if (x < 2) return 0;
     int i = 1, p = 2;
@@ -1191,7 +1202,7 @@ SK_HD void code_ns(Sink& w, int n, int x) {
     }
 }
 
-// palette_mode_info of a key-frame intra block (luma palette; has_palette_uv = 0)
+// palette_mode_info of an intra block (luma palette; has_palette_uv = 0)
 template <class Sink>
 SK_HD void code_palette_mode_info(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int r, int c,
                                   int bsl, const BlkInfo& b) {
@@ -1322,15 +1333,31 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
         if (is_directional(b.uv_mode)) w.sym(cdf_off(cx, cx.angle_delta[b.uv_mode - V_PRED]), 7, 3);
         if (v.screen) code_palette_mode_info(w, cx, v, t, r, c, bsl, b);
     } else {
-        // is_inter: every block of an inter frame is inter, so no neighbour is intra (ctx 0)
-        w.sym(cdf_off(cx, cx.intra_inter[0]), 2, 1);
-        const int nref = (au ? 1 : 0) + (al ? 1 : 0);
-        const int rctx = nref == 0 ? 1 : 2;
+        // is_inter (§8.3.2): an unavailable neighbour counts as inter; both available: 3 if both
+        // are intra, 1 if one is; one available: 2 x (it is intra)
+        const int ai = au && !blk_inter(v.at(r - 1, c)), li = al && !blk_inter(v.at(r, c - 1));
+        const int ictx = au && al ? (ai && li ? 3 : (ai || li ? 1 : 0)) : 2 * (ai | li);
+        w.sym(cdf_off(cx, cx.intra_inter[ictx]), 2, blk_inter(b));
+    }
+    if (!v.key && !blk_inter(b)) {
+        // intra_block_mode_info: y_mode by size group (8x8: 1, 16x16: 2, above: 3), uv_mode,
+        // palette_mode_info; no filter-intra (the sequence header disables it)
+        w.sym(cdf_off(cx, cx.y_mode[sk_min(bsl, 3)]), 13, b.mode);
+        if (is_directional(b.mode)) w.sym(cdf_off(cx, cx.angle_delta[b.mode - V_PRED]), 7, 3);
+        if (bsl <= 3) w.sym(cdf_off(cx, cx.uv_mode_cfl_allowed[b.mode]), 14, b.uv_mode);
+        else w.sym(cdf_off(cx, cx.uv_mode_cfl_not_allowed[b.mode]), 13, b.uv_mode);
+        if (is_directional(b.uv_mode)) w.sym(cdf_off(cx, cx.angle_delta[b.uv_mode - V_PRED]), 7, 3);
+        if (v.screen) code_palette_mode_info(w, cx, v, t, r, c, bsl, b);
+    } else if (!v.key) {
+        // single_ref contexts (§8.3.2 count_refs): only neighbours that are inter count. All
+        // references are forward (p1) and among LAST / LAST2 (p3): a count above zero -> 2, equal
+        // counts -> 1. p4 compares the neighbours on LAST with those on LAST2 (the cached picture)
+        const int an = au && blk_inter(v.at(r - 1, c)), ln = al && blk_inter(v.at(r, c - 1));
+        const int rctx = an + ln == 0 ? 1 : 2;
+        const int n2 = (an ? v.at(r - 1, c).pad1 : 0) + (ln ? v.at(r, c - 1).pad1 : 0), n1 = an + ln - n2;
         w.sym(cdf_off(cx, cx.single_ref[rctx][0]), 2, 0);   // single_ref_p1: forward
         w.sym(cdf_off(cx, cx.single_ref[rctx][2]), 2, 0);   // p3: LAST / LAST2
-        // p4: LAST / LAST2 (the cached picture). A tile's blocks share one reference, so a
-        // neighbour counts for the block's own: LAST2 count above LAST's -> 0, none -> 1
-        w.sym(cdf_off(cx, cx.single_ref[b.pad1 && nref ? 0 : rctx][3]), 2, b.pad1);
+        w.sym(cdf_off(cx, cx.single_ref[n1 < n2 ? 0 : (n1 == n2 ? 1 : 2)][3]), 2, b.pad1);   // p4: LAST / LAST2
         MvStack& s = *v.stk;   // caller's (GPU: LDS; a per-lane array indexed at run time lives in scratch)
         const BlkGrid grid{v.blk, v.geo.c8};
         find_mv_stack(s, grid, t, v.geo.mi_rows, v.geo.mi_cols, r, c, bsl, DecodedBefore{r, c});

@@ -114,7 +114,8 @@ void write_frame_header(BitWriter& w, const Av1Geo& g, const FrameParams& fp) {
     w.put(1, 1);                        // show_frame
     if (!fp.key) w.put(0, 1);           // error_resilient_mode
     w.put(0, 1);                        // disable_cdf_update
-    w.put(fp.screen ? 1 : 0, 1);        // allow_screen_content_tools (palette, key frames)
+    w.put(fp.screen ? 1 : 0, 1);        // allow_screen_content_tools (palette; inter frames: av1_intra_inter).
+                                        // seq_force_integer_mv = 0 in the sequence header: no further bit
     w.put(0, 1);                        // frame_size_override_flag
     if (!fp.key) {
         w.put(7, 3);                    // primary_ref_frame = PRIMARY_REF_NONE
@@ -201,6 +202,8 @@ CpuAv1Encoder::CpuAv1Encoder(const h264::EncoderConfig& cfg, int tcl, int trl) :
     lctx_h[0] = geo.mi_rows;
     lctx_w[1] = lctx_w[2] = geo.mi_cols >> 1;
     pal.assign((size_t)geo.c8 * geo.r8 * 8, 0);
+    jinter.assign((size_t)geo.c8 * geo.r8, 0);
+    intra_inter = cfg.av1_intra_inter > 0;
     lctx_h[1] = lctx_h[2] = geo.mi_rows >> 1;
     for (int p = 0; p < 3; p++) lctx[p].assign((size_t)lctx_w[p] * lctx_h[p], 0);
     level_idx = choose_level_idx(W, H, cfg.fps);
@@ -340,17 +343,23 @@ int intra_mode_decision(const uint8_t* src, int stride, int x, int y, int log2n,
     return best;
 }
 
-void CpuAv1Encoder::intra_block(int r, int c, int bsl, const TileRect& t) {
+// One intra block in `mode` (the open-loop decision), predicted from the reconstruction of its
+// neighbours as it stands: levels, reconstruction and the J of the coding (luma: the cheapest of
+// DCT_DCT, IDTX and the exact palette; chroma: UV_DC_PRED, DCT_DCT) into `o`. Changes no state.
+void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const {
     const h264::Geometry& g = fe.g;
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
     const int log2n = bsl + 2, n = 1 << log2n;
     const int x = c * 4, y = r * 4;
-    BlkInfo b = blk[(size_t)(r >> 1) * geo.c8 + (c >> 1)];   // mode from the decision pass
+    BlkInfo b{};
+    b.bsl = (uint8_t)bsl;
+    b.mode = (uint8_t)mode;
+    b.uv_mode = DC_PRED;
+    int16_t* ly = o.lev;
     IntraEdge ey;
     intra_edges(fe.rec[0].data(), g.stride_y, x, y, n, au, al, geo.mi_cols * 4 - 1, geo.mi_rows * 4 - 1, ey);
     uint8_t py[256];
     intra_predict(ey, b.mode, log2n, py);
-    int16_t* ly = unit_lev(r, c, bsl, 0);
     // luma transform type: DCT_DCT or IDTX (screen content: sharp text codes as samples), by RD cost
     int16_t lid[256];
     const uint8_t* sy = &fe.src[0][(size_t)y * g.stride_y + x];
@@ -359,7 +368,9 @@ void CpuAv1Encoder::intra_block(int r, int c, int bsl, const TileRect& t) {
     b.tx_type = (int16_t)(ji < jd && any_nonzero(lid, n * n) ? TX_IDTX : TX_DCT_DCT);
     if (b.tx_type == TX_IDTX) memcpy(ly, lid, sizeof(int16_t) * n * n);
     b.pal_n = 0;
-    uint8_t col[kPalMax] = {0, 0, 0, 0, 0, 0, 0, 0};
+    o.jy = jd < ji ? jd : ji;
+    uint8_t* col = o.col;
+    memset(col, 0, kPalMax);
     const int k = fp.screen && r + (1 << bsl) <= geo.mi_rows && c + (1 << bsl) <= geo.mi_cols
                       ? palette_colors(sy, g.stride_y, n, col) : 0;
     if (k) {   // exact palette vs the transform path (J of the levels just chosen)
@@ -369,16 +380,16 @@ void CpuAv1Encoder::intra_block(int r, int c, int bsl, const TileRect& t) {
             for (int j = 0; j < n; j++) map[i * n + j] = (uint8_t)palette_index(col, k, sy[(size_t)i * g.stride_y + j]);
         for (int i = 0; i < n; i++)
             for (int j = 0; j < n; j++) rate2 += palette_rate2_px(map, n, i, j, k);
-        if (tx_rd_cost(0, rate2, ac_q(fp.qidx)) < (jd < ji ? jd : ji)) {
+        if (tx_rd_cost(0, rate2, ac_q(fp.qidx)) < o.jy) {
+            o.jy = tx_rd_cost(0, rate2, ac_q(fp.qidx));
             b.pal_n = (uint8_t)k;
             b.mode = DC_PRED;
             b.tx_type = TX_DCT_DCT;
             memset(ly, 0, sizeof(int16_t) * n * n);
             for (int i = 0; i < n; i++) memcpy(&py[i * n], sy + (size_t)i * g.stride_y, (size_t)n);
-            set_palette(r, c, bsl, col);
         }
     }
-    bool nz = recon_block(ly, log2n, fp.qidx, true, b.tx_type, py, &fe.rec[0][(size_t)y * g.stride_y + x], g.stride_y);
+    bool nz = recon_block(ly, log2n, fp.qidx, true, b.tx_type, py, o.rec, n);
     // chroma: UV_DC_PRED. Every other UV mode implies an ADST-family chroma transform
     // (Mode_To_Txfm, §7.13.3 compute_tx_type); this encoder's transforms are DCT_DCT.
     const int cl2 = log2n - 1, cn = n >> 1, cx = x >> 1, cy = y >> 1;
@@ -388,18 +399,79 @@ void CpuAv1Encoder::intra_block(int r, int c, int bsl, const TileRect& t) {
     uint8_t bu[64], bv[64];
     intra_predict(eu, DC_PRED, cl2, bu);
     intra_predict(ev, DC_PRED, cl2, bv);
+    int16_t* lu = o.lev + 256;
+    int16_t* lvv = o.lev + 320;
+    o.jc = quant_block(&fe.src[1][(size_t)cy * g.stride_c + cx], g.stride_c, bu, cl2, fp.qidx, true, TX_DCT_DCT, lu);
+    o.jc += quant_block(&fe.src[2][(size_t)cy * g.stride_c + cx], g.stride_c, bv, cl2, fp.qidx, true, TX_DCT_DCT, lvv);
+    nz |= recon_block(lu, cl2, fp.qidx, true, TX_DCT_DCT, bu, o.rec + 256, cn);
+    nz |= recon_block(lvv, cl2, fp.qidx, true, TX_DCT_DCT, bv, o.rec + 320, cn);
+    b.flags = nz ? 0 : 2;
+    o.b = b;
+}
+
+// Makes an intra coding the block's: reconstruction, levels, level contexts, cells, palette cells.
+void CpuAv1Encoder::intra_commit(int r, int c, int bsl, const IntraCoding& o) {
+    const h264::Geometry& g = fe.g;
+    const int n = 4 << bsl, cn = n >> 1, x = c * 4, y = r * 4, cx = x >> 1, cy = y >> 1;
+    for (int i = 0; i < n; i++) memcpy(&fe.rec[0][(size_t)(y + i) * g.stride_y + x], o.rec + i * n, (size_t)n);
+    for (int i = 0; i < cn; i++) {
+        memcpy(&fe.rec[1][(size_t)(cy + i) * g.stride_c + cx], o.rec + 256 + i * cn, (size_t)cn);
+        memcpy(&fe.rec[2][(size_t)(cy + i) * g.stride_c + cx], o.rec + 320 + i * cn, (size_t)cn);
+    }
+    int16_t* ly = unit_lev(r, c, bsl, 0);
     int16_t* lu = unit_lev(r, c, bsl, 1);
     int16_t* lvv = unit_lev(r, c, bsl, 2);
-    nz |= code_residual(&fe.src[1][(size_t)cy * g.stride_c + cx], g.stride_c, bu, cl2, fp.qidx, true, lu,
-                        &fe.rec[1][(size_t)cy * g.stride_c + cx], g.stride_c);
-    nz |= code_residual(&fe.src[2][(size_t)cy * g.stride_c + cx], g.stride_c, bv, cl2, fp.qidx, true, lvv,
-                        &fe.rec[2][(size_t)cy * g.stride_c + cx], g.stride_c);
-    b.flags = nz ? 0 : 2;
-    set_cells(r, c, bsl, b);
+    memcpy(ly, o.lev, sizeof(int16_t) * n * n);
+    memcpy(lu, o.lev + 256, sizeof(int16_t) * cn * cn);
+    memcpy(lvv, o.lev + 320, sizeof(int16_t) * cn * cn);
+    if (o.b.pal_n) set_palette(r, c, bsl, o.col);
+    set_cells(r, c, bsl, o.b);
+    const bool nz = !blk_skip(o.b);
     const int n4 = 1 << bsl;
     set_lctx(0, c, r, n4, nz ? level_summary(ly, n * n) : 0);
     set_lctx(1, c >> 1, r >> 1, n4 >> 1, nz ? level_summary(lu, cn * cn) : 0);
     set_lctx(2, c >> 1, r >> 1, n4 >> 1, nz ? level_summary(lvv, cn * cn) : 0);
+}
+
+void CpuAv1Encoder::intra_block(int r, int c, int bsl, const TileRect& t) {
+    IntraCoding o;
+    intra_code(r, c, bsl, t, blk[(size_t)(r >> 1) * geo.c8 + (c >> 1)].mode, o);   // mode from the decision pass
+    intra_commit(r, c, bsl, o);
+}
+
+// av1_intra_inter: the block at (r, c), whose inter coding kept levels, as an intra block: mode
+// and palette colours open-loop from the source (intra_mode_decision, palette_colors), predicted
+// from its neighbours' reconstruction as it stands (candidates are visited in coding order; an
+// inter neighbour's reconstruction is final). Kept when its J plus the mode-bits bias is below
+// the inter coding's J (av1_core.h kIntraInterBias2); otherwise nothing changes.
+void CpuAv1Encoder::intra_trial(int r, int c, int bsl, const TileRect& t) {
+    const size_t cell = (size_t)(r >> 1) * geo.c8 + (c >> 1);
+    const BlkInfo& cur = blk[cell];
+    if (!blk_inter(cur) || blk_skip(cur)) return;   // candidates: nonzero levels after the RD skip
+    const int mode = intra_mode_decision(fe.src[0].data(), fe.g.stride_y, c * 4, r * 4, bsl + 2, inside(t, r - 1, c),
+                                         inside(t, r, c - 1), geo.mi_cols * 4 - 1, geo.mi_rows * 4 - 1);
+    IntraCoding o;
+    intra_code(r, c, bsl, t, mode, o);
+    if (o.jy + o.jc + tx_rd_cost(0, kIntraInterBias2, ac_q(fp.qidx)) < jinter[cell]) intra_commit(r, c, bsl, o);
+}
+
+void CpuAv1Encoder::decide_intra_inter() {
+    for (int t = 0; t < geo.tile_cols * geo.tile_rows; t++) {
+        const TileRect tr = tile_rect(geo, t);
+        int ux, uy;
+        for (int i = 0; tile_unit(geo, tr, i, &ux, &uy); i++) {
+            const int r = uy * 4, c = ux * 4;
+            if (r >= geo.mi_rows || c >= geo.mi_cols) continue;
+            if (r + 2 < geo.mi_rows && c + 2 < geo.mi_cols) {
+                intra_trial(r, c, 2, tr);
+                continue;
+            }
+            for (int q = 0; q < 4; q++) {
+                const int rr = r + (q >> 1) * 2, cc = c + (q & 1) * 2;
+                if (rr < geo.mi_rows && cc < geo.mi_cols) intra_trial(rr, cc, 1, tr);
+            }
+        }
+    }
 }
 
 void CpuAv1Encoder::set_palette(int r, int c, int bsl, const uint8_t* col) {
@@ -482,6 +554,7 @@ void CpuAv1Encoder::inter_block(int r, int c, int bsl, int mv_row, int mv_col) {
     // error in one frame: 2x budgets at the QP where it starts)
     if (jz <= (tt == TX_IDTX ? ji : jd))
         for (int p = 0; p < 3; p++) memset(lp[p], 0, sizeof(int16_t) << (2 * ln[p]));
+    jinter[(size_t)(r >> 1) * geo.c8 + (c >> 1)] = tt == TX_IDTX ? ji : jd;   // the J of the coding kept (intra_trial)
     bool nz = recon_block(ly, log2n, fp.qidx, false, tt, py, &fe.rec[0][(size_t)y * g.stride_y + x], g.stride_y);
     nz |= recon_block(lu, log2n - 1, fp.qidx, false, tt, pu, &fe.rec[1][(size_t)cy * g.stride_c + cx], g.stride_c);
     nz |= recon_block(lvv, log2n - 1, fp.qidx, false, tt, pv, &fe.rec[2][(size_t)cy * g.stride_c + cx], g.stride_c);
@@ -524,7 +597,10 @@ void CpuAv1Encoder::decide_inter() {
                 inter_unit(ux, uy, moving ? 8 * m.mvy : 0, moving ? 8 * m.mvx : 0);
             }
     }
-    // static merging: 32x32 then 64x64 blocks whose cells are all skipped with one vector
+}
+
+// static merging: 32x32 then 64x64 inter blocks whose cells are all skipped with one vector
+void CpuAv1Encoder::merge_static() {
     for (int lvl = 3; lvl <= 4; lvl++) {
         const int sz = 1 << lvl, half = sz >> 1;
         for (int r = 0; r < geo.mi_rows; r += sz)
@@ -535,7 +611,7 @@ void CpuAv1Encoder::decide_inter() {
                 for (int y = r >> 1; ok && y < std::min((r + sz) >> 1, geo.r8); y++)
                     for (int x = c >> 1; ok && x < std::min((c + sz) >> 1, geo.c8); x++) {
                         const BlkInfo& b = blk[(size_t)y * geo.c8 + x];
-                        ok = blk_skip(b) && b.mv_row == b0.mv_row && b.mv_col == b0.mv_col;
+                        ok = blk_inter(b) && blk_skip(b) && b.mv_row == b0.mv_row && b.mv_col == b0.mv_col;
                     }
                 if (!ok) continue;
                 BlkInfo m = b0;
@@ -660,7 +736,7 @@ void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, s
         for (int s = 0; s < ns; s++) fe.tasks[s].final_action = ACT_I;
     fe.ctl_.rate_control(fe.tasks.data(), fe.me.data());   // K10
     fp.key = key;
-    fp.screen = key && palette_on;
+    fp.screen = (key || intra_inter) && palette_on;
     if (fe.ltr_cfg.slots) {   // the buffers the header names, from the map before this frame's commit
         const ltr::LtrAv1Bufs b = ltr::ltr_av1_frame_bufs(fe.ltr_cfg, fe.ltr_state[ns], fe.ltr_task.data(), ns);
         fp.refresh = b.refresh;
@@ -684,6 +760,8 @@ void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, s
             decide_key();
         } else {
             decide_inter();
+            if (intra_inter) decide_intra_inter();
+            merge_static();
             decide_modes();
         }
         payload = 0;

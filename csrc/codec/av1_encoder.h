@@ -29,7 +29,7 @@ struct FrameParams {
     int qidx = 86;
     int tile_size_bytes = 4;
     int lf_level = 0;     // loop_filter_level[0..3] (one level, av1_lf.h lf_level_for)
-    int screen = 0;       // allow_screen_content_tools: palette blocks (key frames)
+    int screen = 0;       // allow_screen_content_tools: palette blocks (key frames; inter frames with av1_intra_inter)
     // Reference buffers of an inter frame (long-term cache, ltr.h buffer map; off: buffer 0 throughout)
     int refresh = 0x01;   // refresh_frame_flags: the buffer the picture is written to
     int last_buf = 0;     // ref_frame_idx[0] and [2..6]: the previous picture (LAST)
@@ -103,7 +103,9 @@ class CpuAv1Encoder {
 
     // ---- stages (public for tests / the GPU back end's parity checks) ----
     void decide_key();                        // intra decisions + reconstruction, every tile
-    void decide_inter();                      // motion-compensated units + static merging
+    void decide_inter();                      // motion-compensated units
+    void decide_intra_inter();                // av1_intra_inter: units that kept a residual, tried as intra blocks
+    void merge_static();                      // static 32x32 / 64x64 merging
     void decide_modes();                      // inter modes from the MV stacks (pass A)
     std::vector<uint8_t> code_tile(int t);    // arithmetic-coded tile payload
     std::vector<uint8_t> assemble(const std::vector<std::vector<uint8_t>>& tiles);
@@ -116,6 +118,8 @@ class CpuAv1Encoder {
     std::vector<uint8_t> lctx[3];    // level contexts (cul | dc << 6) at 4x4 granularity per plane
     std::vector<uint8_t> pal;        // c8 * r8 * 8: palette colours of each cell's block
     bool palette_on = palette_enabled();
+    bool intra_inter = false;        // EncoderConfig::av1_intra_inter
+    std::vector<long long> jinter;   // c8 * r8: J of the inter coding of the block at that origin cell (inter_block)
     int lctx_w[3] = {0, 0, 0}, lctx_h[3] = {0, 0, 0};
     int level_idx = 8;
     uint64_t frames = 0;
@@ -124,6 +128,17 @@ class CpuAv1Encoder {
     FrameView view() const;
 
    private:
+    // An intra coding of one block, not yet the block's: luma at 0, U at 256, V at 320 (raster per plane)
+    struct IntraCoding {
+        BlkInfo b;
+        int16_t lev[384];
+        uint8_t rec[384];
+        uint8_t col[kPalMax];
+        long long jy, jc;   // tx_rd_cost of the luma coding kept and of both chroma planes
+    };
+    void intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const;
+    void intra_commit(int r, int c, int bsl, const IntraCoding& o);
+    void intra_trial(int r, int c, int bsl, const TileRect& t);
     void intra_block(int r, int c, int bsl, const TileRect& t);
     void inter_unit(int ux, int uy, int mv_row, int mv_col);
     void inter_block(int r, int c, int bsl, int mv_row, int mv_col);

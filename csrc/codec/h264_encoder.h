@@ -62,6 +62,8 @@ struct EncoderConfig {
                                  // by default like x264's ultrafast preset (partitions none)
     int ltr_slots = 0;           // long-term reference cache (ltr.h): pictures kept per stream for content that comes
                                  // back (window switches); 0 = off, 1..8 (AV1: 1..7); H.264: excludes num_refs > 1
+    int av1_intra_inter = 0;     // AV1: blocks of an inter frame whose inter coding left a residual are also tried as
+                                 // intra blocks (luma palettes included, av1_core.h); the other codecs ignore it
 };
 
 // Long-term cache slots in force (the three codecs share this configuration and the front end).

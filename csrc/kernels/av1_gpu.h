@@ -13,7 +13,7 @@ namespace av1 {
 namespace gpu {
 
 constexpr int kLevPerUnit = 384;
-constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2707, below)
+constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2711, below)
 constexpr int kTileChunkCap = 1 << 20;
 
 // The most tokens code_unit (av1_core.h; k_av1_tokens) can put into one unit's slot, over every
@@ -44,14 +44,15 @@ constexpr int kInterHead = 1 + 1 + 3                        // skip, is_inter, t
 constexpr int kPaletteMap = 64 - 1 + 1 + 1;                 // an 8x8 block: the other 63 indices, the first as literal bits, its flush
 constexpr int kPartition = 2 + 1 + 4;                       // the 64 and 32 nodes the unit opens, its own, four 8x8 nodes
 constexpr int kBlocks = 4;
-constexpr int kHead = kKeyHead + kPaletteMap > kInterHead ? kKeyHead + kPaletteMap : kInterHead;
+constexpr int kIntraHead = kKeyHead + 1;                    // an intra block of an inter frame: is_inter too (av1_intra_inter)
+constexpr int kHead = kIntraHead + kPaletteMap > kInterHead ? kIntraHead + kPaletteMap : kInterHead;
 constexpr int kUnit = kPartition                            // partition symbols
                       + kBlocks * kHead                     // mode info (and index maps) of four blocks
                       + kTxbs * kTxbHead                    // per transform block
                       + kCoefs * (1 + 4)                    // coeff_base(_eob) + four coeff_br per level
                       + kCoefs * kCoefBits / 24;            // full literals of the sign / Golomb runs
 static_assert(kCoefBits == 24 && 256 * kCoefBits <= 256 * 32, "a 16x16 block's sign / Golomb run fits the 256-word LDS bit buffer");
-static_assert(kUnit == 2707, "tok_bound changed: update the comment on kTokCap");
+static_assert(kUnit == 2711, "tok_bound changed: update the comment on kTokCap");
 static_assert(kUnit <= kTokCap, "a unit's tokens can overflow its slot (the tokens past it are dropped)");
 }   // namespace tok_bound
 
@@ -61,9 +62,14 @@ struct Av1Args {
     BlkInfo* blk;             // [r8][c8]
     uint8_t* pal;             // [r8][c8][8] palette colours of each cell's block (key frames)
     int palette;              // palette coding of key frames enabled (av1_encoder.h palette_enabled)
-    int* pal_rate;            // [r8][c8] key frames: palette_rate2 of the block at that origin cell
-                              // (k_av1_intra_modes; its colour count rides in BlkInfo.pad1 until
-                              // k_av1_intra_rec decides)
+    int* pal_rate;            // [r8][c8] palette_rate2 of the block at that origin cell (key frames:
+                              // k_av1_intra_modes; its colour count rides in BlkInfo.pad1 until
+                              // k_av1_intra_rec decides; inter frames: k_av1_cand_modes, count in cand)
+    int intra_inter;          // EncoderConfig::av1_intra_inter: intra blocks in inter frames; the three below only then
+    long long* jinter;        // [r8][c8] J of the inter coding of the block at that origin cell (k_av1_inter)
+    int* cand;                // [r8][c8] bit 0: the block is an intra candidate (its inter coding kept levels),
+                              // bits 8..15 its open-loop mode, bits 16..19 its palette colour count (k_av1_cand_modes)
+    int* tile_cand;           // [tiles] candidates of the tile (k_av1_setup clears, k_av1_inter counts)
     int16_t* lev;             // [units][kLevPerUnit]
     uint8_t* lctx[3];         // level contexts per plane (4x4 units), strides lctx_w
     int lctx_w[3];

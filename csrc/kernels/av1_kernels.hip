@@ -6,6 +6,10 @@
 //                      prediction never crosses a tile edge), anti-diagonal steps x + y
 //   k_av1_inter        inter frames: motion compensation (8-tap / 4-tap sub-pel chroma),
 //                      transform, quantisation, reconstruction, one wave per unit
+//   k_av1_cand_modes   inter frames with av1_intra_inter: open-loop intra mode and palette candidate of
+//                      every block whose inter coding kept levels, one wave per unit
+//   k_av1_inter_intra  the same frames: those blocks as intra blocks, one workgroup per tile on the
+//                      key frame's wavefront; kept where the intra J is below the inter coding's
 //   k_av1_merge        inter frames: static 32x32 / 64x64 merging, one wave per superblock
 //   k_av1_modes        inter frames: reference-MV stack -> NEAREST / NEAR / GLOBAL / NEWMV
 //   k_av1_tokens       block syntax -> token lists, one wave per 16x16 unit (coefficients lane-parallel)
@@ -75,7 +79,8 @@ struct BlkLds {
     int32_t b[384];
     int16_t lv[384];     // quantised levels (raster per plane) before tail trimming
     int16_t lv2[384];    // IDTX levels of the same residual (the transform-type decision)
-    long long jreg;      // intra: the luma J of the cheaper transform type (palette decision)
+    long long jreg;      // intra: the luma J of the cheaper transform type (palette decision); kJ = 1: the inter coding's J
+    long long jchr;      // kJ = 2: the J of both chroma planes of an intra block
     IntraEdge e[3];      // intra edges of Y, U, V
 };
 // Tile of a unit position (mi r, c).
@@ -154,6 +159,10 @@ __device__ int rate2_wave(const int16_t* lv, int ln) {
 // luma only, chroma DCT_DCT). Writes levels to gl (3 planes), the reconstruction into
 // L.pred, and returns the per-plane level summaries (cul | dc << 6) packed as bytes
 // 0..2, bit 24 = any nonzero, bit 25 = IDTX.
+// kJ (av1_intra_inter): 1 = an inter block that leaves the three-plane J its RD skip compared in
+// L.jreg; 2 = an intra block on trial: the chroma J into L.jchr too, and no level goes to gy / gu /
+// gv (the final levels stay in L.lv for the caller to store if the block is kept).
+template <int kJ = 0>
 __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int qidx, bool intra, int16_t* gy,
                                     int16_t* gu, int16_t* gv) {
     const int l = lane();
@@ -218,6 +227,10 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
             wsync();   // the plane's levels, for the rate estimates
             jd += tx_rd_cost(4 * dp, rate2_wave(L.lv + o, ln), qa);
             ji += tx_rd_cost(4 * ip, rate2_wave(L.lv2 + o, ln), qa);
+        } else if (kJ == 2) {   // through LDS, like jreg below: no accumulator live across the planes
+            wsync();
+            const long long jp = tx_rd_cost(4 * dp, rate2_wave(L.lv + o, ln), qa);
+            if (l == 0) L.jchr = p == 1 ? jp : L.jchr + jp;
         }
     }
     wsync();
@@ -245,6 +258,7 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
             for (int i = l; i < m; i += 64) L.lv[o + i] = L.lv2[o + i];
         }
     // inter RD skip (av1_cpu.cpp inter_block): nothing coded when the levels do not pay
+    if (kJ == 1 && l == 0) L.jreg = idtx ? ji : jd;
     if (!intra && jz <= (idtx ? ji : jd))
         for (int p = 0; p < 3; p++) {
             const int m = p ? cnn : nn, o = base(p);
@@ -265,7 +279,7 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
         for (int i = l; i < sz * sz; i += 64) {
             const int q = i == 0 ? qd : qa;
             const int lv = L.lv[o + i];
-            g[i] = (int16_t)lv;
+            if (kJ != 2) g[i] = (int16_t)lv;
             if (i == 0) first = lv;
             sum += lv < 0 ? -lv : lv;
             nz |= lv;
@@ -455,6 +469,8 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
             f.tasks[s].final_action = ACT_I;
             f.tasks_host[s].final_action = ACT_I;
         }
+    if (A.intra_inter)   // candidates per tile, counted by k_av1_inter
+        for (int t = threadIdx.x; t < A.geo.tile_cols * A.geo.tile_rows; t += 256) A.tile_cand[t] = 0;
     if (threadIdx.x == 0) {
         // K10: the frame's fractional QP under CRF / CBR (slices dither on H.264 / HEVC)
         const int qidx = f.rc->mode == h264::RC_CQP ? A.qidx_of_qp[sk_clip(f.tasks[0].qp, 0, 51)]
@@ -477,6 +493,73 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
     }
 }
 
+// Open-loop intra mode of the block at (r, c) from the source edges, by one wave (E, seen, map, col:
+// the wave's LDS). Palette candidate (source only, so decided here in parallel rather than in the
+// reconstruction wavefront): the block's distinct luma values, its colours into the palette
+// cells, palette_rate2 into pal_rate for the RD comparison of the reconstruction. *pal_k: the
+// colour count of the candidate (0: none).
+__device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdge& E, uint32_t* seen, uint8_t* map,
+                               uint8_t* col, int* pal_k) {
+    const FrameArgs& f = A.f;
+    const Av1Geo& g = A.geo;
+    const int l = lane(), log2n = bsl + 2, n = 1 << log2n;
+    const TileRect t = tile_of(g, r, c);
+    const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
+    if (l == 0) intra_edges(f.src.y, f.stride_y, c * 4, r * 4, n, au, al, g.mi_cols * 4 - 1, g.mi_rows * 4 - 1, E);
+    wsync();
+    const int dc = intra_dc(E, log2n);
+    const uint8_t cand[7] = {DC_PRED, V_PRED, H_PRED, SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, PAETH_PRED};
+    int best = DC_PRED, best_cost = 1 << 30;
+    for (int m = 0; m < 7; m++) {
+        int sad = 0;
+        for (int i = l; i < n * n; i += 64) {
+            const int pr = cand[m] == DC_PRED ? dc : intra_pred_px(E, cand[m], log2n, i / n, i % n);
+            sad += sk_abs((int)f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n] - pr);
+        }
+        sad = wsum(sad);
+        const int cost = sad + (cand[m] == DC_PRED ? 0 : n * 2);
+        if (cost < best_cost) {
+            best_cost = cost;
+            best = cand[m];
+        }
+    }
+    *pal_k = 0;
+    if (A.palette && r + (1 << bsl) <= g.mi_rows && c + (1 << bsl) <= g.mi_cols) {
+        if (l < 8) seen[l] = 0u;
+        wsync();
+        for (int i = l; i < n * n; i += 64) {
+            const int v = f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n];
+            atomicOr(&seen[v >> 5], 1u << (v & 31));
+        }
+        wsync();
+        const int k = wsum(l < 8 ? __builtin_popcount(seen[l]) : 0);
+        if (k >= 2 && k <= kPalMax) {
+            if (l == 0) {
+                int q = 0;
+                for (int v = 0; v < 256; v++)
+                    if ((seen[v >> 5] >> (v & 31)) & 1) col[q++] = (uint8_t)v;
+                for (; q < 8; q++) col[q] = 0;
+            }
+            wsync();
+            for (int i = l; i < n * n; i += 64)
+                map[i] = (uint8_t)palette_index(col, k, f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]);
+            wsync();
+            int r2 = 0;
+            for (int i = l; i < n * n; i += 64) r2 += palette_rate2_px(map, n, i / n, i % n, k);
+            r2 = wsum(r2) + palette_rate2_head(k);
+            const int n8 = (1 << bsl) >> 1;
+            for (int i = l; i < n8 * n8 * 8; i += 64) {
+                const int cell = i >> 3, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
+                A.pal[((size_t)ry * g.c8 + cx) * 8 + (i & 7)] = col[i & 7];
+            }
+            if (l == 0) A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2;
+            *pal_k = k;
+        }
+        wsync();
+    }
+    return best;
+}
+
 // Key frames: intra mode per block from the source edges (one wave per unit).
 __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
@@ -486,7 +569,7 @@ __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
     if (!A.frame[0]) return;
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
-    const int w = threadIdx.x >> 6, l = lane();
+    const int w = threadIdx.x >> 6;
     const int u = blockIdx.x * 4 + w;
     if (u >= f.mb_w * f.mb_h) return;
     const int ux = u % f.mb_w, uy = u / f.mb_w;
@@ -494,86 +577,75 @@ __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
     const int bsl = nb < 0 ? 2 : 1;
     if (nb < 0) nb = 1;
     for (int k = 0; k < nb; k++) {
-        int r, c;
+        int r, c, pal_k;
         unit_block(g, uy, ux, k, r, c);
-        const int log2n = bsl + 2, n = 1 << log2n;
-        const TileRect t = tile_of(g, r, c);
-        const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
-        if (l == 0) intra_edges(f.src.y, f.stride_y, c * 4, r * 4, n, au, al, g.mi_cols * 4 - 1, g.mi_rows * 4 - 1, E[w]);
-        wsync();
-        const int dc = intra_dc(E[w], log2n);
-        const uint8_t cand[7] = {DC_PRED, V_PRED, H_PRED, SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, PAETH_PRED};
-        int best = DC_PRED, best_cost = 1 << 30;
-        for (int m = 0; m < 7; m++) {
-            int sad = 0;
-            for (int i = l; i < n * n; i += 64) {
-                const int pr = cand[m] == DC_PRED ? dc : intra_pred_px(E[w], cand[m], log2n, i / n, i % n);
-                sad += sk_abs((int)f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n] - pr);
-            }
-            sad = wsum(sad);
-            const int cost = sad + (cand[m] == DC_PRED ? 0 : n * 2);
-            if (cost < best_cost) {
-                best_cost = cost;
-                best = cand[m];
-            }
-        }
         BlkInfo b{};
         b.bsl = (uint8_t)bsl;
-        b.mode = (uint8_t)best;
+        b.mode = (uint8_t)intra_mode_wave(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
         b.uv_mode = DC_PRED;
-        // palette candidate (source only, so decided here in parallel rather than in the
-        // reconstruction wavefront): the block's distinct luma values, its colours into
-        // the palette cells, palette_rate2 for k_av1_intra_rec's RD comparison
-        if (A.palette && r + (1 << bsl) <= g.mi_rows && c + (1 << bsl) <= g.mi_cols) {
-            uint32_t* seen = pal_seen[w];
-            uint8_t* map = pal_map[w];
-            uint8_t* col = pal_col[w];
-            if (l < 8) seen[l] = 0u;
-            wsync();
-            for (int i = l; i < n * n; i += 64) {
-                const int v = f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n];
-                atomicOr(&seen[v >> 5], 1u << (v & 31));
-            }
-            wsync();
-            const int k = wsum(l < 8 ? __builtin_popcount(seen[l]) : 0);
-            if (k >= 2 && k <= kPalMax) {
-                if (l == 0) {
-                    int q = 0;
-                    for (int v = 0; v < 256; v++)
-                        if ((seen[v >> 5] >> (v & 31)) & 1) col[q++] = (uint8_t)v;
-                    for (; q < 8; q++) col[q] = 0;
-                }
-                wsync();
-                for (int i = l; i < n * n; i += 64)
-                    map[i] = (uint8_t)palette_index(col, k, f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]);
-                wsync();
-                int r2 = 0;
-                for (int i = l; i < n * n; i += 64) r2 += palette_rate2_px(map, n, i / n, i % n, k);
-                r2 = wsum(r2) + palette_rate2_head(k);
-                const int n8 = (1 << bsl) >> 1;
-                for (int i = l; i < n8 * n8 * 8; i += 64) {
-                    const int cell = i >> 3, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
-                    A.pal[((size_t)ry * g.c8 + cx) * 8 + (i & 7)] = col[i & 7];
-                }
-                if (l == 0) A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2;
-                b.pad1 = (uint8_t)k;
-            }
-            wsync();
-        }
+        b.pad1 = (uint8_t)pal_k;   // the candidate's colour count rides in the cell until k_av1_intra_rec decides
         set_cells(A, r, c, bsl, b);
         wsync();
     }
 }
 
-// Reconstruction of one intra block (mode from the cells) by one wave.
-__device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, int r, int c, int bsl, int qidx) {
+// Inter frames with av1_intra_inter: the same decision for every block whose inter coding kept
+// levels (k_av1_inter's cells: inter and not skipped), one wave per unit. The cells stay the inter
+// coding's, so the mode and the colour count travel in A.cand: bit 0 candidate, bits 8..15 the
+// mode, bits 16..19 the palette candidate's colour count.
+__global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
+    if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
+    __shared__ IntraEdge E[4];
+    __shared__ uint32_t pal_seen[4][8];
+    __shared__ uint8_t pal_map[4][256], pal_col[4][8];
+    if (A.frame[0]) return;
+    const FrameArgs& f = A.f;
+    const Av1Geo& g = A.geo;
+    const int w = threadIdx.x >> 6;
+    const int u = blockIdx.x * 4 + w;
+    if (u >= f.mb_w * f.mb_h) return;
+    const int ux = u % f.mb_w, uy = u / f.mb_w;
+    int nb = unit_blocks(g, uy, ux);
+    const int bsl = nb < 0 ? 2 : 1;
+    if (nb < 0) nb = 1;
+    for (int k = 0; k < nb; k++) {
+        int r, c, pal_k;
+        unit_block(g, uy, ux, k, r, c);
+        const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
+        const BlkInfo b = A.blk[cell];
+        int cand = 0;
+        if (blk_inter(b) && !blk_skip(b)) {   // wave-uniform
+            const int mode = intra_mode_wave(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
+            cand = 1 | (mode << 8) | (pal_k << 16);
+        }
+        if (lane() == 0) A.cand[cell] = cand;
+        wsync();
+    }
+}
+
+// Reconstruction of one intra block by one wave. Key frames: mode and palette candidate from the
+// cells (cand = -1). kTrial (av1_intra_inter, inter frames): both from cand (k_av1_cand_modes);
+// the block is worked out in LDS and becomes the block's coding - reconstruction, levels, level
+// contexts, cells - only where its J plus the mode-bits bias is below the inter coding's
+// (av1_cpu.cpp intra_trial); otherwise nothing is stored.
+template <bool kTrial>
+__device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, int r, int c, int bsl, int qidx, int cand) {
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
     const int l = lane(), log2n = bsl + 2, n = 1 << log2n, cn = n >> 1;
     const int x = c * 4, y = r * 4;
     const TileRect t = tile_of(g, r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
-    BlkInfo b = A.blk[(size_t)(r >> 1) * g.c8 + (c >> 1)];
+    const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
+    BlkInfo b{};
+    if (kTrial) {
+        b.bsl = (uint8_t)bsl;
+        b.mode = (uint8_t)(cand >> 8);
+        b.uv_mode = DC_PRED;
+        b.pad1 = (uint8_t)((cand >> 16) & 15);
+    } else {
+        b = A.blk[cell];
+    }
     IntraEdge* E = L.e;
     if (l == 0) {
         intra_edges(f.rec.y, f.stride_y, x, y, n, au, al, g.mi_cols * 4 - 1, g.mi_rows * 4 - 1, E[0]);
@@ -590,27 +662,38 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         L.pred[320 + i] = (uint8_t)dcv;
     }
     wsync();
-    uint32_t s = code_block_wave(L, F, log2n, qidx, true, lev_ptr(A, r, c, bsl, 0), lev_ptr(A, r, c, bsl, 1),
-                                 lev_ptr(A, r, c, bsl, 2));
-    const long long jreg = L.jreg;
+    uint32_t s = code_block_wave<kTrial ? 2 : 0>(L, F, log2n, qidx, true, lev_ptr(A, r, c, bsl, 0),
+                                                 lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
+    long long jreg = L.jreg;
     b.tx_type = (int16_t)((s >> 25) & 1 ? TX_IDTX : TX_DCT_DCT);
     // palette candidate from k_av1_intra_modes (colours already in the palette cells):
     // exact palette of the source luma vs the transform path (av1_cpu.cpp intra_block)
     const int kc = b.pad1;
     b.pad1 = 0;
     b.pal_n = 0;
-    if (kc && tx_rd_cost(0, A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)], ac_q(qidx)) < jreg) {
+    if (kc && tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx)) < jreg) {
+        jreg = tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx));
         b.pal_n = (uint8_t)kc;
         b.mode = DC_PRED;
         b.tx_type = TX_DCT_DCT;
         int16_t* gy = lev_ptr(A, r, c, bsl, 0);
         for (int i = l; i < n * n; i += 64) {
-            gy[i] = 0;
+            if (kTrial) L.lv[i] = 0;
+            else gy[i] = 0;
             L.pred[i] = L.src[i];
         }
         s &= ~0xffu;   // no luma levels: the summary and the skip flag come from chroma
         s = (s & ~(1u << 24)) | ((s & 0xffff00u) ? (1u << 24) : 0u);
         wsync();
+    }
+    if (kTrial) {
+        // wave-uniform: every lane reads the same words
+        if (!(jreg + L.jchr + tx_rd_cost(0, kIntraInterBias2, ac_q(qidx)) < A.jinter[cell])) return;
+        for (int p = 0; p < 3; p++) {
+            int16_t* gp = lev_ptr(A, r, c, bsl, p);
+            const int m = p ? cn * cn : n * n, o = p == 0 ? 0 : (p == 1 ? 256 : 320);
+            for (int i = l; i < m; i += 64) gp[i] = L.lv[o + i];
+        }
     }
     store_rec_blk(L, f, x, y, n);
     b.flags = (s >> 24) & 1 ? 0 : 2;
@@ -648,7 +731,49 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
             for (int k = 0; k < nb; k++) {
                 int r, c;
                 unit_block(g, uy0 + y, ux0 + x, k, r, c);
-                intra_rec_block(A, Lw[w], F, r, c, bsl, qidx);
+                intra_rec_block<false>(A, Lw[w], F, r, c, bsl, qidx, -1);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Inter frames with av1_intra_inter, after k_av1_inter and k_av1_cand_modes: the blocks whose
+// inter coding kept levels, tried as intra blocks in coding order. One workgroup (16 waves) per
+// tile on k_av1_intra_rec's wavefront: a candidate predicts from its neighbours' reconstruction
+// as it stands (an inter neighbour's is final, a candidate neighbour's was decided at an earlier
+// step). A tile without candidates returns before loading anything; a unit without one costs
+// its wave nothing but the step's barrier.
+__global__ __launch_bounds__(1024) void k_av1_inter_intra(Av1Args A) {
+    if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
+    __shared__ BlkLds Lw[16];
+    __shared__ FdctLds F;
+    if (A.frame[0]) return;
+    const Av1Geo& g = A.geo;
+    const int t = blockIdx.x;
+    if (A.tile_cand[t] == 0) return;
+    const TileRect tr = tile_rect(g, t);
+    load_fdct(F);
+    __syncthreads();
+    // the wave index as a scalar: the block position, its candidate word and the decision are
+    // wave-uniform and stay out of the vector registers the transforms need
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int ux0 = tr.mi_col0 >> 2, uy0 = tr.mi_row0 >> 2;
+    const int uw = (tr.mi_col1 - tr.mi_col0 + 3) >> 2, uh = (tr.mi_row1 - tr.mi_row0 + 3) >> 2;
+    const int qidx = A.frame[1];
+    const int steps = uw + uh - 1;
+    for (int s = 0; s < steps; s++) {
+        for (int y = w; y < uh; y += 16) {
+            const int x = s - y;
+            if (x < 0 || x >= uw) continue;
+            int nb = unit_blocks(g, uy0 + y, ux0 + x);
+            const int bsl = nb < 0 ? 2 : 1;
+            if (nb < 0) nb = 1;
+            for (int k = 0; k < nb; k++) {
+                int r, c;
+                unit_block(g, uy0 + y, ux0 + x, k, r, c);
+                const int cand = A.cand[(size_t)(r >> 1) * g.c8 + (c >> 1)];
+                if (cand & 1) intra_rec_block<true>(A, Lw[w], F, r, c, bsl, qidx, cand);
             }
         }
         __syncthreads();
@@ -656,8 +781,10 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
 }
 
 // Inter frames: one wave per unit, vector from the front end's motion search. kLtr: the
-// long-term cache is on (ltr.h); off, the kernel is the one-reference kernel it was.
-template <bool kLtr>
+// long-term cache is on (ltr.h); off, the kernel is the one-reference kernel it was. kJ
+// (av1_intra_inter): the J of each block's coding into A.jinter, and the blocks that kept levels
+// (the intra candidates) counted per tile.
+template <bool kLtr, bool kJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_av1_inter(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[4];
@@ -698,8 +825,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         mc_block(ref.u, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 256);
         mc_block(ref.v, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 320);
         wsync();
-        const uint32_t s = code_block_wave(L, F, log2n, qidx, false, lev_ptr(A, r, c, bsl, 0),
-                                           lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
+        const uint32_t s = code_block_wave<kJ ? 1 : 0>(L, F, log2n, qidx, false, lev_ptr(A, r, c, bsl, 0),
+                                                       lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
+        if (kJ && l == 0) {
+            A.jinter[(size_t)(r >> 1) * g.c8 + (c >> 1)] = L.jreg;
+            if ((s >> 24) & 1) atomicAdd(&A.tile_cand[((r >> 4) / g.tile_h_sb) * g.tile_cols + (c >> 4) / g.tile_w_sb], 1);
+        }
         store_rec_blk(L, f, x, y, n);
         BlkInfo b{};
         b.bsl = (uint8_t)bsl;
@@ -734,7 +865,7 @@ __global__ __launch_bounds__(64) void k_av1_merge(Av1Args A) {
         const bool fits = r + sz <= g.mi_rows && c + sz <= g.mi_cols;
         const BlkInfo b0 = A.blk[(size_t)(r >> 1) * g.c8 + (c >> 1)];
         const BlkInfo me = in ? A.blk[(size_t)cy * g.c8 + cx] : b0;
-        const bool ok_me = !in || (blk_skip(me) && me.mv_row == b0.mv_row && me.mv_col == b0.mv_col);
+        const bool ok_me = !in || (blk_inter(me) && blk_skip(me) && me.mv_row == b0.mv_row && me.mv_col == b0.mv_col);
         // all lanes of the region must agree: reduce over the region's lanes
         const uint64_t bad = __ballot(!ok_me);
         uint64_t mask = 0;
@@ -764,7 +895,7 @@ __global__ __launch_bounds__(256) void k_av1_modes(Av1Args A) {
     const int y8 = cell / g.c8, x8 = cell % g.c8;
     const BlkInfo b = A.blk[cell];
     const int n8 = (1 << b.bsl) >> 1;
-    if ((y8 & (n8 - 1)) || (x8 & (n8 - 1))) return;
+    if (!blk_inter(b) || (y8 & (n8 - 1)) || (x8 & (n8 - 1))) return;   // inter blocks, origin cells only
     const int r = y8 * 2, c = x8 * 2;
     const TileRect t = tile_of(g, r, c);
     MvStack& s = stk[threadIdx.x];   // LDS: a per-lane stack indexed at run time would live in scratch
@@ -1090,7 +1221,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     v.unit_w = f.mb_w;
     v.qidx = A.frame[1];
     v.key = A.frame[0];
-    v.screen = A.frame[0] && A.palette;
+    v.screen = (A.frame[0] || A.intra_inter) && A.palette;
     v.pal = A.pal;
     v.src_y = f.src.y;
     v.stride_y = f.stride_y;
@@ -1777,8 +1908,17 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_modes, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_rec, dim3(tiles), dim3(1024), 0, s, a);
-    if (a.f.ltr_cfg.mode == ltr::LTR_BUFMAP) hipLaunchKernelGGL(k_av1_inter<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_av1_inter<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    const bool ltr_on = a.f.ltr_cfg.mode == ltr::LTR_BUFMAP;
+    if (a.intra_inter) {   // av1_intra_inter: the inter coding with its J, then the candidates as intra blocks
+        if (ltr_on) hipLaunchKernelGGL((k_av1_inter<true, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_av1_inter<false, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_av1_cand_modes, dim3((n + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_av1_inter_intra, dim3(tiles), dim3(1024), 0, s, a);
+    } else if (ltr_on) {
+        hipLaunchKernelGGL((k_av1_inter<true, false>), dim3((n + 3) / 4), dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_av1_inter<false, false>), dim3((n + 3) / 4), dim3(256), 0, s, a);
+    }
     hipLaunchKernelGGL(k_av1_merge, dim3(a.geo.sb_cols * a.geo.sb_rows), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_av1_modes, dim3((a.geo.c8 * a.geo.r8 + 255) / 256), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_tokens, dim3((n + 3) / 4), dim3(256), 0, s, a);

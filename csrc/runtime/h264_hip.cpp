@@ -970,6 +970,12 @@ class HipBackend : public EncoderBackend {
         a.pal = mem_.dmalloc<uint8_t>((size_t)av1_geo_.c8 * av1_geo_.r8 * 8);
         a.palette = av1::palette_enabled() ? 1 : 0;
         a.pal_rate = mem_.dmalloc<int>((size_t)av1_geo_.c8 * av1_geo_.r8);
+        a.intra_inter = cfg_.av1_intra_inter > 0;
+        if (a.intra_inter) {   // av1_gpu.h: the inter coding's J, the intra candidates and their count per tile
+            a.jinter = mem_.dmalloc<long long>((size_t)av1_geo_.c8 * av1_geo_.r8);
+            a.cand = mem_.dmalloc<int>((size_t)av1_geo_.c8 * av1_geo_.r8);
+            a.tile_cand = mem_.dmalloc<int>((size_t)av1_geo_.tile_cols * av1_geo_.tile_rows);
+        }
         a.lev = mem_.dmalloc<int16_t>((size_t)n * av1::gpu::kLevPerUnit);
         a.lctx_w[0] = av1_geo_.mi_cols;
         a.lctx_w[1] = a.lctx_w[2] = av1_geo_.mi_cols >> 1;
@@ -1027,7 +1033,7 @@ class HipBackend : public EncoderBackend {
             fp.last_buf = f.av1_frame.host[4];
             fp.last2_buf = f.av1_frame.host[5];
         }
-        fp.screen = fp.key && aargs_.palette;
+        fp.screen = (fp.key || aargs_.intra_inter) && aargs_.palette;
         std::vector<std::vector<uint8_t>> tl(tiles);
         size_t off = 0;
         for (int t = 0; t < tiles; t++) {

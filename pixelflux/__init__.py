@@ -61,6 +61,7 @@ def default_settings(width: int = 1920, height: int = 1080, **kw) -> CaptureSett
     s.step_mode = 0
     s.pool = None
     s.pool_frames = s.pool_stride = s.pool_phase = 0
+    s.av1_intra_inter = 0   # AV1 sessions: intra blocks and luma palettes in inter frames (off)
     for k, v in kw.items():
         if isinstance(v, str):
             v = v.encode()
