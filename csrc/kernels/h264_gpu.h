@@ -21,6 +21,12 @@ struct Planes {
 };
 
 // Everything a kernel needs, passed by value (pointers are device memory).
+// One struct for all codecs of the HIP back end. The buffers of the H.264 coding chain (mbs,
+// coefs, mb_bits, mb_nbits, slice_info, param_sets, param_set_len, host_out, host_size,
+// cavlc_tabs, aq, db, dbe) are allocated by the H.264 tail alone (runtime/h264_tail.h) and null
+// in HEVC and AV1 sessions: the kernels those launch (launch_convert_damage, launch_frontend,
+// launch_rc_account, launch_rc_guard_sizes, k_commit without `account` and with deblock 0)
+// must not touch them.
 struct FrameArgs {
     int W, H, mb_w, mb_h, stride_y, stride_c, num_slices, rows_per_slice, fullframe;
     int full_range, me_range, me_iters;
