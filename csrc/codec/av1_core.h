@@ -16,8 +16,9 @@
 //   TX_MODE_LARGEST (one transform per block, reduced_tx_set: DCT_DCT or IDTX, the
 //   screen-content identity transform, chosen per luma block); intra DC / V / H /
 //   SMOOTH(_V/_H) / PAETH / directional, luma palettes of 2..8 colours
-//   (code_palette_mode_info / code_palette_tokens), no filter-intra / CfL / chroma
-//   palette / intraBC, intra edge filter off; one reference per block (LAST, or LAST2 for
+//   (code_palette_mode_info / code_palette_tokens) and, with av1_chroma_palette, exact chroma
+//   palettes of 2..8 (U, V) pairs on the same blocks (chroma is UV_DC_PRED + DCT_DCT otherwise);
+//   no filter-intra / CfL / intraBC, intra edge filter off; one reference per block (LAST, or LAST2 for
 //   the cached picture of ltr.h), single prediction, EIGHTTAP regular filter, quarter-pel
 //   vectors (allow_high_precision_mv = 0); no order hints (no temporal MVs, no skip mode);
 //   in-loop deblocking (av1_lf.h) and CDEF (av1_cdef.h) on, loop restoration off.
@@ -85,12 +86,15 @@ struct BlkInfo {
     uint8_t flags;     // bit0 is_inter, bit1 skip, bit2 merged-static (encoder), bits 4-5 RefMvIdx
     int16_t mv_row, mv_col;   // 1/8 pel (LAST), even values (no high-precision MVs)
     int16_t tx_type;   // luma transform type: TX_DCT_DCT (0) or TX_IDTX (1); inter chroma follows it
-    uint8_t pal_n;     // PaletteSizeY (0: no palette; colours in the frame's palette cells)
+    uint8_t pal_n;     // low nibble PaletteSizeY, high nibble PaletteSizeUV (0: no palette; colours in the frame's
+                       // palette cells); read through pal_ny / pal_nuv
     uint8_t pad1;      // inter frames: the block's reference, 0 = LAST, 1 = LAST2 (the cached picture, ltr.h)
 };
 static_assert(sizeof(BlkInfo) == 12, "BlkInfo layout");
 SK_HD bool blk_inter(const BlkInfo& b) { return (b.flags & 1) != 0; }
 SK_HD bool blk_skip(const BlkInfo& b) { return (b.flags & 2) != 0; }
+SK_HD int pal_ny(const BlkInfo& b) { return b.pal_n & 15; }
+SK_HD int pal_nuv(const BlkInfo& b) { return b.pal_n >> 4; }
 
 // ---------------------------------------------------------------------------------
 // Transforms. Forward: encoder choice, an integer DCT-II scaled to 8x the
@@ -1050,9 +1054,14 @@ struct FrameView {
     const uint8_t* pal;          // [r8][c8][8] palette colours of each cell's block
     const uint8_t* src_y;        // source luma: the colour index map of a palette block
     int stride_y;
+    const uint8_t* pal_uv;       // [r8][c8][16] chroma palette of each cell's block: U colours at 0, V at 8 (pair q: [q], [8 + q])
+    const uint8_t* src_u;        // source chroma: the colour index map of a chroma palette block
+    const uint8_t* src_v;
+    int stride_c;
     MvStack* stk = nullptr;      // the reference MV stack's storage (set by the caller; GPU: this wave's LDS slot)
     SK_HD const BlkInfo& at(int r, int c) const { return blk[(r >> 1) * geo.c8 + (c >> 1)]; }
     SK_HD const uint8_t* pal_at(int r, int c) const { return pal + ((size_t)(r >> 1) * geo.c8 + (c >> 1)) * 8; }
+    SK_HD const uint8_t* pal_uv_at(int r, int c) const { return pal_uv + ((size_t)(r >> 1) * geo.c8 + (c >> 1)) * 16; }
     // levels of the block at mi (r, c) of size bsl in plane p (raster [row][col])
     SK_HD const int16_t* levels(int r, int c, int bsl, int p) const {
         const int16_t* u = lev + ((size_t)(r >> 2) * unit_w + (c >> 2)) * 384;
@@ -1097,8 +1106,8 @@ SK_HD CoefCtx coef_ctx(const FrameView& v, const TileRect& t, int plane, int x4,
 
 // ---------------------------------------------------------------------------------
 // Palette (screen content tools; §5.11.46 palette_mode_info, §5.11.49 palette_tokens,
-// §7.11.4 get_palette_cache / get_palette_color_context), luma only: intra blocks of key
-// frames and, with av1_intra_inter, of inter frames.
+// §7.11.4 get_palette_cache / get_palette_color_context): intra blocks of key frames and, with
+// av1_intra_inter, of inter frames; luma always, chroma with av1_chroma_palette (further below).
 // Encoder choice (av1_cpu.cpp intra_block = k_av1_intra_rec): a fully visible block
 // whose source luma takes 2..8 distinct values can be coded as that exact palette, with
 // no luma residual, when palette_rate2's cost is below the transform path's J.
@@ -1121,8 +1130,8 @@ SK_HD int ceil_log2(int x) {
 // PaletteCache: the sorted union of the above (only inside the same 64-row superblock
 // row) and left blocks' palettes, duplicates dropped. Returns its size.
 SK_HD int palette_cache(const FrameView& v, const TileRect& t, int r, int c, uint8_t* cache) {
-    const int an = inside(t, r - 1, c) && (r & 15) ? v.at(r - 1, c).pal_n : 0;
-    const int ln = inside(t, r, c - 1) ? v.at(r, c - 1).pal_n : 0;
+    const int an = inside(t, r - 1, c) && (r & 15) ? pal_ny(v.at(r - 1, c)) : 0;
+    const int ln = inside(t, r, c - 1) ? pal_ny(v.at(r, c - 1)) : 0;
     const uint8_t* ac = an ? v.pal_at(r - 1, c) : nullptr;
     const uint8_t* lc = ln ? v.pal_at(r, c - 1) : nullptr;
     int ai = 0, li = 0, n = 0;
@@ -1202,14 +1211,155 @@ SK_HD void code_ns(Sink& w, int n, int x) {
     }
 }
 
-// palette_mode_info of an intra block (luma palette; has_palette_uv = 0)
+// Chroma palette (av1_chroma_palette): 2..8 (U, V) pairs sorted by (U, V), held as two packed
+// words (pair q: byte q of U and of V) so that no code path indexes an array at run time (GPU).
+SK_HD int pal_byte(uint64_t x, int q) { return (int)((x >> (8 * q)) & 255u); }
+SK_HD uint64_t pal_load8(const uint8_t* p) {
+    uint64_t x = 0;
+    for (int q = 0; q < 8; q++) x |= (uint64_t)p[q] << (8 * q);
+    return x;
+}
+// PaletteCache of plane 1: palette_cache's merge over the above and left blocks' U colours
+// (ascending, equal values possible) with their PaletteSizeUV, up to 16 entries packed into lo
+// (entries 0..7) and hi. Returns its size.
+SK_HD int palette_cache_uv(const FrameView& v, const TileRect& t, int r, int c, uint64_t* lo, uint64_t* hi) {
+    const int an = inside(t, r - 1, c) && (r & 15) ? pal_nuv(v.at(r - 1, c)) : 0;
+    const int ln = inside(t, r, c - 1) ? pal_nuv(v.at(r, c - 1)) : 0;
+    const uint64_t A = an ? pal_load8(v.pal_uv_at(r - 1, c)) : 0, L = ln ? pal_load8(v.pal_uv_at(r, c - 1)) : 0;
+    uint64_t w0 = 0, w1 = 0;
+    int ai = 0, li = 0, n = 0, last = -1;
+    while (ai < an || li < ln) {
+        const int a = ai < an ? pal_byte(A, ai) : 256, l = li < ln ? pal_byte(L, li) : 256;
+        const int x = l < a ? l : a;
+        if (l < a) {
+            li++;
+        } else {
+            ai++;
+            if (l == a) li++;
+        }
+        if (x != last) {
+            if (n < 8) w0 |= (uint64_t)x << (8 * n);
+            else w1 |= (uint64_t)x << (8 * (n - 8));
+            n++;
+        }
+        last = x;
+    }
+    *lo = w0;
+    *hi = w1;
+    return n;
+}
+// Index of the pair (u, v) in a block's pairs.
+SK_HD int palette_index_uv(uint64_t U, uint64_t V, int k, int u, int v) {
+    int x = 0;
+    for (int q = 0; q < k; q++) x = pal_byte(U, q) == u && pal_byte(V, q) == v ? q : x;
+    return x;
+}
+
+// The colour literals of a chroma palette after the cache flags (bit q of from_cache: U colour q
+// came from the cache). U: the others ascending, the first in 8 bits, then deltas (not offset:
+// equal values are legal) in 5 + palette_num_extra_bits_u bits, shrinking with the range left.
+// V in U order: delta coded (fixed width 4 + palette_num_extra_bits_v, sign after a nonzero
+// magnitude, modulo 256) when every wrapped |delta| <= 127 and that costs fewer bits, else raw.
 template <class Sink>
+SK_HD void code_palette_uv_literals(Sink& w, uint64_t U, uint64_t V, int k, uint32_t from_cache) {
+    int need = 0, m = 0, p = 0;
+    for (int q = 0; q < k; q++)
+        if (!((from_cache >> q) & 1)) {
+            const int x = pal_byte(U, q);
+            if (m > 0) need = sk_max(need, ceil_log2(x - p + 1));
+            p = x;
+            m++;
+        }
+    int bits = 0;
+    m = 0;
+    for (int q = 0; q < k; q++)
+        if (!((from_cache >> q) & 1)) {
+            const int x = pal_byte(U, q);
+            if (m == 0) {
+                w.lits((uint32_t)x, 8);
+            } else {
+                if (m == 1) {
+                    const int extra = sk_max(need - 5, 0);
+                    w.lits((uint32_t)extra, 2);
+                    bits = 5 + extra;
+                }
+                w.lits((uint32_t)(x - p), bits);
+                bits = sk_min(bits, ceil_log2(256 - x));
+            }
+            p = x;
+            m++;
+        }
+    bool wraps = true;
+    int vneed = 0, nz = 0;
+    for (int q = 1; q < k; q++) {
+        const int dm = (pal_byte(V, q) - pal_byte(V, q - 1)) & 255, mag = dm <= 127 ? dm : 256 - dm;
+        wraps &= dm != 128;
+        vneed = sk_max(vneed, ceil_log2(mag + 1));
+        nz += mag != 0;
+    }
+    const int vw = sk_max(vneed, 4);
+    const bool delta = wraps && 2 + 8 + (k - 1) * vw + nz < 8 * k;
+    w.bit(delta);
+    if (delta) {
+        w.lits((uint32_t)(vw - 4), 2);
+        w.lits((uint32_t)pal_byte(V, 0), 8);
+        for (int q = 1; q < k; q++) {
+            const int dm = (pal_byte(V, q) - pal_byte(V, q - 1)) & 255, mag = dm <= 127 ? dm : 256 - dm;
+            w.lits((uint32_t)mag, vw);
+            if (mag) w.bit(dm > 127);
+        }
+    } else {
+        for (int q = 0; q < k; q++) w.lits((uint32_t)pal_byte(V, q), 8);
+    }
+}
+// Counts the bits a sink would get.
+struct BitCountSink {
+    int n = 0;
+    SK_HD void bit(int) { n++; }
+    SK_HD void lits(uint32_t, int nbits) { n += nbits; }
+};
+// Encoder: rate (half bits) of a chroma palette's head: has_palette_uv and the size symbol as
+// 1 + 3 bits, the colour literals exactly, without credit for the cache.
+SK_HD int palette_uv_rate2_head(uint64_t U, uint64_t V, int k) {
+    BitCountSink s;
+    code_palette_uv_literals(s, U, V, k, 0u);
+    return 2 * (1 + 3 + s.n);
+}
+
+// Encoder: the distinct (U, V) pairs of the cn x cn chroma block at (su, sv), sorted by (U, V), when
+// there are 2..kPalMax of them (returns the count, else 0). Host side; the kernels find them per wave.
+inline int palette_colors_uv(const uint8_t* su, const uint8_t* sv, int stride, int cn, uint64_t* U, uint64_t* V) {
+    int key[kPalMax + 1], k = 0;
+    for (int i = 0; i < cn; i++)
+        for (int j = 0; j < cn; j++) {
+            const int x = (su[(size_t)i * stride + j] << 8) | sv[(size_t)i * stride + j];
+            int q = 0;
+            while (q < k && key[q] < x) q++;
+            if (q < k && key[q] == x) continue;
+            if (k == kPalMax) return 0;
+            for (int s = k; s > q; s--) key[s] = key[s - 1];
+            key[q] = x;
+            k++;
+        }
+    if (k < 2) return 0;
+    *U = *V = 0;
+    for (int q = 0; q < k; q++) {
+        *U |= (uint64_t)(key[q] >> 8) << (8 * q);
+        *V |= (uint64_t)(key[q] & 255) << (8 * q);
+    }
+    return k;
+}
+
+// palette_mode_info of an intra block: the luma palette, then (uv_mode is DC_PRED) the chroma palette.
+// kUv = false compiles the chroma palette's syntax out (has_palette_uv = 0): the GPU token kernel of
+// sessions without av1_chroma_palette.
+template <class Sink, bool kUv = true>
 SK_HD void code_palette_mode_info(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int r, int c,
                                   int bsl, const BlkInfo& b) {
     const int bctx = 2 * bsl - 2;   // Mi_Width_Log2 + Mi_Height_Log2 - 2 (square blocks)
-    const int k = b.pal_n;
+    const int k = pal_ny(b);
     if (b.mode == DC_PRED) {
-        const int ctx = (inside(t, r - 1, c) && v.at(r - 1, c).pal_n > 0) + (inside(t, r, c - 1) && v.at(r, c - 1).pal_n > 0);
+        const int ctx = (inside(t, r - 1, c) && pal_ny(v.at(r - 1, c)) > 0) + (inside(t, r, c - 1) && pal_ny(v.at(r, c - 1)) > 0);
         w.sym(cdf_off(cx, cx.palette_y_mode[bctx][ctx]), 2, k > 0);
         if (k > 0) {
             w.sym(cdf_off(cx, cx.palette_y_size[bctx]), 7, k - 2);
@@ -1246,7 +1396,30 @@ SK_HD void code_palette_mode_info(Sink& w, const CdfContext& cx, const FrameView
             }
         }
     }
-    if (b.uv_mode == DC_PRED) w.sym(cdf_off(cx, cx.palette_uv_mode[k > 0]), 2, 0);
+    if (b.uv_mode == DC_PRED) {
+        const int kuv = kUv ? pal_nuv(b) : 0;
+        w.sym(cdf_off(cx, cx.palette_uv_mode[k > 0]), 2, kuv > 0);
+        if (kuv > 0) {
+            w.sym(cdf_off(cx, cx.palette_uv_size[bctx]), 7, kuv - 2);
+            const uint8_t* cuv = v.pal_uv_at(r, c);
+            const uint64_t U = pal_load8(cuv), V = pal_load8(cuv + 8);
+            uint64_t clo, chi;
+            const int cn = palette_cache_uv(v, t, r, c, &clo, &chi);
+            uint32_t from_cache = 0;   // a cache colour takes one of its occurrences in U (the lowest index)
+            int idx = 0;
+            for (int i = 0; i < cn && idx < kuv; i++) {
+                const int cc = i < 8 ? pal_byte(clo, i) : pal_byte(chi, i - 8);
+                int hit = -1;
+                for (int q = kuv - 1; q >= 0; q--) hit = pal_byte(U, q) == cc ? q : hit;
+                w.bit(hit >= 0);
+                if (hit >= 0) {
+                    from_cache |= 1u << hit;
+                    idx++;
+                }
+            }
+            code_palette_uv_literals(w, U, V, kuv, from_cache);
+        }
+    }
 }
 
 // palette_tokens: the colour index map, first index as ns(k), then every other sample on
@@ -1266,6 +1439,29 @@ SK_HD void code_palette_tokens(Sink& w, const CdfContext& cx, const FrameView& v
             uint32_t order;
             const int ctx = palette_color_context(map, n, i, j, k, &order);
             w.sym(cdf_off(cx, cx.palette_y_color[k - 2][ctx]), k, palette_rank(order, k, map[i * n + j]));
+        }
+}
+
+// The chroma part of palette_tokens: one index map for both planes over the (n/2) x (n/2) chroma
+// block, coded like the luma map with the uv colour CDFs.
+template <class Sink>
+SK_HD void code_palette_tokens_uv(Sink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl, int k) {
+    const int n = 2 << bsl;
+    const uint8_t* cuv = v.pal_uv_at(r, c);
+    const uint64_t U = pal_load8(cuv), V = pal_load8(cuv + 8);
+    uint8_t map[64];
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            const size_t o = (size_t)(r * 2 + i) * v.stride_c + c * 2 + j;
+            map[i * n + j] = (uint8_t)palette_index_uv(U, V, k, v.src_u[o], v.src_v[o]);
+        }
+    code_ns(w, k, map[0]);
+    for (int d = 1; d < 2 * n - 1; d++)
+        for (int j = sk_min(d, n - 1); j >= sk_max(0, d - n + 1); j--) {
+            const int i = d - j;
+            uint32_t order;
+            const int ctx = palette_color_context(map, n, i, j, k, &order);
+            w.sym(cdf_off(cx, cx.palette_uv_color[k - 2][ctx]), k, palette_rank(order, k, map[i * n + j]));
         }
 }
 
@@ -1318,7 +1514,7 @@ struct DecodedBefore {
 };
 
 // Mode info + residual of one block (§5.11.5 decode_block).
-template <class Sink>
+template <class Sink, bool kUv = true>
 SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int r, int c, int bsl) {
     const BlkInfo& b = v.at(r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
@@ -1331,7 +1527,7 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
         if (bsl <= 3) w.sym(cdf_off(cx, cx.uv_mode_cfl_allowed[b.mode]), 14, b.uv_mode);
         else w.sym(cdf_off(cx, cx.uv_mode_cfl_not_allowed[b.mode]), 13, b.uv_mode);
         if (is_directional(b.uv_mode)) w.sym(cdf_off(cx, cx.angle_delta[b.uv_mode - V_PRED]), 7, 3);
-        if (v.screen) code_palette_mode_info(w, cx, v, t, r, c, bsl, b);
+        if (v.screen) code_palette_mode_info<Sink, kUv>(w, cx, v, t, r, c, bsl, b);
     } else {
         // is_inter (§8.3.2): an unavailable neighbour counts as inter; both available: 3 if both
         // are intra, 1 if one is; one available: 2 x (it is intra)
@@ -1347,7 +1543,7 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
         if (bsl <= 3) w.sym(cdf_off(cx, cx.uv_mode_cfl_allowed[b.mode]), 14, b.uv_mode);
         else w.sym(cdf_off(cx, cx.uv_mode_cfl_not_allowed[b.mode]), 13, b.uv_mode);
         if (is_directional(b.uv_mode)) w.sym(cdf_off(cx, cx.angle_delta[b.uv_mode - V_PRED]), 7, 3);
-        if (v.screen) code_palette_mode_info(w, cx, v, t, r, c, bsl, b);
+        if (v.screen) code_palette_mode_info<Sink, kUv>(w, cx, v, t, r, c, bsl, b);
     } else if (!v.key) {
         // single_ref contexts (§8.3.2 count_refs): only neighbours that are inter count. All
         // references are forward (p1) and among LAST / LAST2 (p3): a count above zero -> 2, equal
@@ -1385,7 +1581,8 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
             code_mv(w, cx, b.mv_row - s.mv[pos][0], b.mv_col - s.mv[pos][1]);
         }
     }
-    if (b.pal_n) code_palette_tokens(w, cx, v, r, c, bsl, b.pal_n);
+    if (pal_ny(b)) code_palette_tokens(w, cx, v, r, c, bsl, pal_ny(b));
+    if (kUv && pal_nuv(b)) code_palette_tokens_uv(w, cx, v, r, c, bsl, pal_nuv(b));
     if (blk_skip(b)) return;
     code_coeffs(w, cx, v.levels(r, c, bsl, 0), bsl, 0, coef_ctx(v, t, 0, c, r, 1 << bsl), blk_inter(b), b.mode, v.qidx,
                 b.tx_type);
@@ -1418,7 +1615,7 @@ SK_HD bool code_partition_symbol(Sink& w, const CdfContext& cx, const FrameView&
 // partition symbols of the 64 / 32 nodes it opens, then its own block(s); a unit
 // inside a larger (merged) block contributes nothing. Units in Z order within
 // raster superblocks reproduce decode_partition's order exactly.
-template <class Sink>
+template <class Sink, bool kUv = true>
 SK_HD void code_unit(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int ux, int uy) {
     const int r = uy * 4, c = ux * 4;
     if (r >= v.geo.mi_rows || c >= v.geo.mi_cols) return;
@@ -1430,19 +1627,19 @@ SK_HD void code_unit(Sink& w, const CdfContext& cx, const FrameView& v, const Ti
             continue;
         }
         if (code_partition_symbol(w, cx, v, t, r, c, L)) {
-            code_block(w, cx, v, t, r, c, L);
+            code_block<Sink, kUv>(w, cx, v, t, r, c, L);
             return;
         }
     }
     if (code_partition_symbol(w, cx, v, t, r, c, 2)) {
-        code_block(w, cx, v, t, r, c, 2);
+        code_block<Sink, kUv>(w, cx, v, t, r, c, 2);
         return;
     }
     for (int q = 0; q < 4; q++) {
         const int rr = r + (q >> 1) * 2, cc = c + (q & 1) * 2;
         if (rr >= v.geo.mi_rows || cc >= v.geo.mi_cols) continue;
         code_partition_symbol(w, cx, v, t, rr, cc, 1);
-        code_block(w, cx, v, t, rr, cc, 1);
+        code_block<Sink, kUv>(w, cx, v, t, rr, cc, 1);
     }
 }
 

@@ -202,6 +202,8 @@ CpuAv1Encoder::CpuAv1Encoder(const h264::EncoderConfig& cfg, int tcl, int trl) :
     lctx_h[0] = geo.mi_rows;
     lctx_w[1] = lctx_w[2] = geo.mi_cols >> 1;
     pal.assign((size_t)geo.c8 * geo.r8 * 8, 0);
+    pal_uv.assign((size_t)geo.c8 * geo.r8 * 16, 0);
+    chroma_palette = cfg.av1_chroma_palette > 0;
     jinter.assign((size_t)geo.c8 * geo.r8, 0);
     intra_inter = cfg.av1_intra_inter > 0;
     lctx_h[1] = lctx_h[2] = geo.mi_rows >> 1;
@@ -345,7 +347,8 @@ int intra_mode_decision(const uint8_t* src, int stride, int x, int y, int log2n,
 
 // One intra block in `mode` (the open-loop decision), predicted from the reconstruction of its
 // neighbours as it stands: levels, reconstruction and the J of the coding (luma: the cheapest of
-// DCT_DCT, IDTX and the exact palette; chroma: UV_DC_PRED, DCT_DCT) into `o`. Changes no state.
+// DCT_DCT, IDTX and the exact palette; chroma: UV_DC_PRED, DCT_DCT, or with av1_chroma_palette the
+// exact palette where that is cheaper) into `o`. Changes no state.
 void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const {
     const h264::Geometry& g = fe.g;
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
@@ -371,8 +374,8 @@ void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mod
     o.jy = jd < ji ? jd : ji;
     uint8_t* col = o.col;
     memset(col, 0, kPalMax);
-    const int k = fp.screen && r + (1 << bsl) <= geo.mi_rows && c + (1 << bsl) <= geo.mi_cols
-                      ? palette_colors(sy, g.stride_y, n, col) : 0;
+    const bool visible = r + (1 << bsl) <= geo.mi_rows && c + (1 << bsl) <= geo.mi_cols;
+    const int k = fp.screen && visible ? palette_colors(sy, g.stride_y, n, col) : 0;
     if (k) {   // exact palette vs the transform path (J of the levels just chosen)
         uint8_t map[256];
         int rate2 = palette_rate2_head(k);
@@ -403,6 +406,31 @@ void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mod
     int16_t* lvv = o.lev + 320;
     o.jc = quant_block(&fe.src[1][(size_t)cy * g.stride_c + cx], g.stride_c, bu, cl2, fp.qidx, true, TX_DCT_DCT, lu);
     o.jc += quant_block(&fe.src[2][(size_t)cy * g.stride_c + cx], g.stride_c, bv, cl2, fp.qidx, true, TX_DCT_DCT, lvv);
+    // chroma palette (av1_chroma_palette): the exact (U, V) pairs of the source vs both DCT planes
+    const uint8_t* su = &fe.src[1][(size_t)cy * g.stride_c + cx];
+    const uint8_t* sv = &fe.src[2][(size_t)cy * g.stride_c + cx];
+    o.col_u = o.col_v = 0;
+    const int kuv = fp.screen && chroma_palette && visible ? palette_colors_uv(su, sv, g.stride_c, cn, &o.col_u, &o.col_v) : 0;
+    if (kuv) {
+        uint8_t map[64];
+        int rate2 = palette_uv_rate2_head(o.col_u, o.col_v, kuv);
+        for (int i = 0; i < cn; i++)
+            for (int j = 0; j < cn; j++)
+                map[i * cn + j] = (uint8_t)palette_index_uv(o.col_u, o.col_v, kuv, su[(size_t)i * g.stride_c + j],
+                                                            sv[(size_t)i * g.stride_c + j]);
+        for (int i = 0; i < cn; i++)
+            for (int j = 0; j < cn; j++) rate2 += palette_rate2_px(map, cn, i, j, kuv);
+        if (tx_rd_cost(0, rate2, ac_q(fp.qidx)) < o.jc) {
+            o.jc = tx_rd_cost(0, rate2, ac_q(fp.qidx));
+            b.pal_n = (uint8_t)(b.pal_n | (kuv << 4));
+            memset(lu, 0, sizeof(int16_t) * cn * cn);
+            memset(lvv, 0, sizeof(int16_t) * cn * cn);
+            for (int i = 0; i < cn; i++) {
+                memcpy(&bu[i * cn], su + (size_t)i * g.stride_c, (size_t)cn);
+                memcpy(&bv[i * cn], sv + (size_t)i * g.stride_c, (size_t)cn);
+            }
+        }
+    }
     nz |= recon_block(lu, cl2, fp.qidx, true, TX_DCT_DCT, bu, o.rec + 256, cn);
     nz |= recon_block(lvv, cl2, fp.qidx, true, TX_DCT_DCT, bv, o.rec + 320, cn);
     b.flags = nz ? 0 : 2;
@@ -424,7 +452,8 @@ void CpuAv1Encoder::intra_commit(int r, int c, int bsl, const IntraCoding& o) {
     memcpy(ly, o.lev, sizeof(int16_t) * n * n);
     memcpy(lu, o.lev + 256, sizeof(int16_t) * cn * cn);
     memcpy(lvv, o.lev + 320, sizeof(int16_t) * cn * cn);
-    if (o.b.pal_n) set_palette(r, c, bsl, o.col);
+    if (pal_ny(o.b)) set_palette(r, c, bsl, o.col);
+    if (pal_nuv(o.b)) set_palette_uv(r, c, bsl, o.col_u, o.col_v);
     set_cells(r, c, bsl, o.b);
     const bool nz = !blk_skip(o.b);
     const int n4 = 1 << bsl;
@@ -480,6 +509,20 @@ void CpuAv1Encoder::set_palette(int r, int c, int bsl, const uint8_t* col) {
         for (int x = 0; x < n8; x++) {
             const int ry = (r >> 1) + y, cx = (c >> 1) + x;
             if (ry < geo.r8 && cx < geo.c8) memcpy(&pal[((size_t)ry * geo.c8 + cx) * 8], col, kPalMax);
+        }
+}
+
+void CpuAv1Encoder::set_palette_uv(int r, int c, int bsl, uint64_t u, uint64_t v) {
+    const int n8 = (1 << bsl) >> 1;
+    for (int y = 0; y < n8; y++)
+        for (int x = 0; x < n8; x++) {
+            const int ry = (r >> 1) + y, cx = (c >> 1) + x;
+            if (ry >= geo.r8 || cx >= geo.c8) continue;
+            uint8_t* d = &pal_uv[((size_t)ry * geo.c8 + cx) * 16];
+            for (int q = 0; q < kPalMax; q++) {
+                d[q] = (uint8_t)pal_byte(u, q);
+                d[8 + q] = (uint8_t)pal_byte(v, q);
+            }
         }
 }
 
@@ -668,6 +711,10 @@ FrameView CpuAv1Encoder::view() const {
     v.pal = pal.data();
     v.src_y = fe.src[0].data();
     v.stride_y = fe.g.stride_y;
+    v.pal_uv = pal_uv.data();
+    v.src_u = fe.src[1].data();
+    v.src_v = fe.src[2].data();
+    v.stride_c = fe.g.stride_c;
     return v;
 }
 

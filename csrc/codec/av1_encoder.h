@@ -117,8 +117,10 @@ class CpuAv1Encoder {
     std::vector<int16_t> lev;        // kLevPerUnit per 16x16 unit (front-end MB grid)
     std::vector<uint8_t> lctx[3];    // level contexts (cul | dc << 6) at 4x4 granularity per plane
     std::vector<uint8_t> pal;        // c8 * r8 * 8: palette colours of each cell's block
+    std::vector<uint8_t> pal_uv;     // c8 * r8 * 16: chroma palette of each cell's block, U at 0, V at 8 (av1_chroma_palette)
     bool palette_on = palette_enabled();
     bool intra_inter = false;        // EncoderConfig::av1_intra_inter
+    bool chroma_palette = false;     // EncoderConfig::av1_chroma_palette (acts where palettes do: fp.screen)
     std::vector<long long> jinter;   // c8 * r8: J of the inter coding of the block at that origin cell (inter_block)
     int lctx_w[3] = {0, 0, 0}, lctx_h[3] = {0, 0, 0};
     int level_idx = 8;
@@ -134,6 +136,7 @@ class CpuAv1Encoder {
         int16_t lev[384];
         uint8_t rec[384];
         uint8_t col[kPalMax];
+        uint64_t col_u, col_v;   // chroma palette pairs (av1_core.h pal_byte), PaletteSizeUV in b
         long long jy, jc;   // tx_rd_cost of the luma coding kept and of both chroma planes
     };
     void intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const;
@@ -146,6 +149,7 @@ class CpuAv1Encoder {
     void set_cells(int r, int c, int bsl, const BlkInfo& b);
     void set_lctx(int plane, int x4, int y4, int n4, uint8_t v);
     void set_palette(int r, int c, int bsl, const uint8_t* col);
+    void set_palette_uv(int r, int c, int bsl, uint64_t u, uint64_t v);
 };
 
 }  // namespace av1

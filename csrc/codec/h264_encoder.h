@@ -64,6 +64,8 @@ struct EncoderConfig {
                                  // back (window switches); 0 = off, 1..8 (AV1: 1..7); H.264: excludes num_refs > 1
     int av1_intra_inter = 0;     // AV1: blocks of an inter frame whose inter coding left a residual are also tried as
                                  // intra blocks (luma palettes included, av1_core.h); the other codecs ignore it
+    int av1_chroma_palette = 0;  // AV1: exact chroma palettes of 2..8 (U, V) pairs on intra blocks, where luma palettes may
+                                 // occur (key frames; inter frames with av1_intra_inter); the other codecs ignore it
 };
 
 // Long-term cache slots in force (the three codecs share this configuration and the front end).

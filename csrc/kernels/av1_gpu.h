@@ -13,7 +13,7 @@ namespace av1 {
 namespace gpu {
 
 constexpr int kLevPerUnit = 384;
-constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2711, below)
+constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2815, below)
 constexpr int kTileChunkCap = 1 << 20;
 
 // The most tokens code_unit (av1_core.h; k_av1_tokens) can put into one unit's slot, over every
@@ -33,15 +33,21 @@ constexpr int kTxbs = 4 * 3;                                // transform blocks 
 constexpr int kTxbHead = 1 + 1 + 1 + 1 + 1 + 1 + 1;         // txb_skip, tx set, eob_pt, eob_extra, its literal bits, dc_sign, the
                                                             // bits left over after the block's full 24-bit literals
 constexpr int kPaletteBits = 16 + 8 + 2 + 7 * 8;            // cache flags, first colour, extra bits, seven deltas
+constexpr int kPaletteUvBits = kPaletteBits                 // U: cache flags, first colour, extra bits, seven deltas
+                               + 1 + 8 * 8;                 // V: the delta flag, eight raw colours (delta coding only where shorter)
 constexpr int kKeyHead = 1 + 1 + 1 + 1 + 1                  // skip, y mode, angle delta, uv mode, angle delta
                          + 1 + 1                            // palette_y_mode, palette_y_size
                          + (kPaletteBits + 23) / 24 + 1     // the colours' literals (the first may join pending bits)
-                         + 1;                               // palette_uv_mode
+                         + 1                                // palette_uv_mode
+                         + 1                                // palette_uv_size (av1_chroma_palette)
+                         + (kPaletteUvBits + 23) / 24 + 1;  // the chroma colours' literals
 constexpr int kMvComp = 1 + 1 + 10 + 1;                     // sign, class, class bits, fraction
 constexpr int kInterHead = 1 + 1 + 3                        // skip, is_inter, three single_ref symbols
                            + 1 + 2                          // new_mv, two drl symbols (zero_mv / ref_mv: without a vector)
                            + 1 + 2 * kMvComp;               // mv_joint, both components
-constexpr int kPaletteMap = 64 - 1 + 1 + 1;                 // an 8x8 block: the other 63 indices, the first as literal bits, its flush
+constexpr int kPaletteMap = 64 - 1 + 1 + 1                  // an 8x8 block: the other 63 indices, the first as literal bits, its flush
+                            + 16 - 1 + 1 + 1;               // its 4x4 chroma map likewise (a 16x16 block's two maps, 257 + 65
+                                                            // tokens, stay below four 8x8 blocks')
 constexpr int kPartition = 2 + 1 + 4;                       // the 64 and 32 nodes the unit opens, its own, four 8x8 nodes
 constexpr int kBlocks = 4;
 constexpr int kIntraHead = kKeyHead + 1;                    // an intra block of an inter frame: is_inter too (av1_intra_inter)
@@ -52,7 +58,7 @@ constexpr int kUnit = kPartition                            // partition symbols
                       + kCoefs * (1 + 4)                    // coeff_base(_eob) + four coeff_br per level
                       + kCoefs * kCoefBits / 24;            // full literals of the sign / Golomb runs
 static_assert(kCoefBits == 24 && 256 * kCoefBits <= 256 * 32, "a 16x16 block's sign / Golomb run fits the 256-word LDS bit buffer");
-static_assert(kUnit == 2711, "tok_bound changed: update the comment on kTokCap");
+static_assert(kUnit == 2815, "tok_bound changed: update the comment on kTokCap");
 static_assert(kUnit <= kTokCap, "a unit's tokens can overflow its slot (the tokens past it are dropped)");
 }   // namespace tok_bound
 
@@ -65,6 +71,11 @@ struct Av1Args {
     int* pal_rate;            // [r8][c8] palette_rate2 of the block at that origin cell (key frames:
                               // k_av1_intra_modes; its colour count rides in BlkInfo.pad1 until
                               // k_av1_intra_rec decides; inter frames: k_av1_cand_modes, count in cand)
+    int chroma_palette;       // EncoderConfig::av1_chroma_palette (and palette): chroma palettes on the blocks above
+    uint8_t* pal_uv;          // [r8][c8][16] chroma palette of each cell's block: U at 0, V at 8 (av1_core.h FrameView)
+    int* pal_rate_uv;         // [r8][c8] rate (half bits) of the chroma palette candidate of the block at that origin
+                              // cell; its pair count rides in the high nibble of BlkInfo.pad1 (key frames) or in
+                              // bits 20..23 of cand (inter frames)
     int intra_inter;          // EncoderConfig::av1_intra_inter: intra blocks in inter frames; the three below only then
     long long* jinter;        // [r8][c8] J of the inter coding of the block at that origin cell (k_av1_inter)
     int* cand;                // [r8][c8] bit 0: the block is an intra candidate (its inter coding kept levels),

@@ -22,6 +22,8 @@
 //   k_av1_lf           in-loop deblocking (codec/av1_lf.h), one launch per plane and pass
 //   k_av1_cdef         CDEF (codec/av1_cdef.h), one wave per 8x8, from a copy of the deblocked picture
 //   k_av1_finish       padding rows of the reconstruction, slice actions for k_commit
+// av1_chroma_palette selects the <true> instantiations of k_av1_intra_modes / cand_modes / intra_rec /
+// inter_intra / tokens (chroma candidate, decision and syntax); <false> is the kernel without them.
 // Transforms: forward DCT as LDS matrix products (lanes = output coefficients),
 // inverse as the normative butterflies, lane = row / column of a transform block.
 #include <cstring>
@@ -54,6 +56,11 @@ __device__ __forceinline__ int wsum(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+__device__ __forceinline__ int wmin(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = sk_min(v, __shfl_xor(v, o));
+    return v;
+}
 
 // Forward DCT bases in LDS: [0] 4-point at 0, 8-point at 16, 16-point at 80.
 struct FdctLds {
@@ -80,7 +87,7 @@ struct BlkLds {
     int16_t lv[384];     // quantised levels (raster per plane) before tail trimming
     int16_t lv2[384];    // IDTX levels of the same residual (the transform-type decision)
     long long jreg;      // intra: the luma J of the cheaper transform type (palette decision); kJ = 1: the inter coding's J
-    long long jchr;      // kJ = 2: the J of both chroma planes of an intra block
+    long long jchr;      // kJ = 2: the J of both chroma planes of an intra block (trial; chroma palette decision)
     IntraEdge e[3];      // intra edges of Y, U, V
 };
 // Tile of a unit position (mi r, c).
@@ -160,8 +167,9 @@ __device__ int rate2_wave(const int16_t* lv, int ln) {
 // L.pred, and returns the per-plane level summaries (cul | dc << 6) packed as bytes
 // 0..2, bit 24 = any nonzero, bit 25 = IDTX.
 // kJ (av1_intra_inter): 1 = an inter block that leaves the three-plane J its RD skip compared in
-// L.jreg; 2 = an intra block on trial: the chroma J into L.jchr too, and no level goes to gy / gu /
-// gv (the final levels stay in L.lv for the caller to store if the block is kept).
+// L.jreg; 2 = an intra block on trial, or one that may take a chroma palette: the chroma J into
+// L.jchr too, and no level goes to gy / gu / gv (the final levels stay in L.lv for the caller to
+// store if the block is kept).
 template <int kJ = 0>
 __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int qidx, bool intra, int16_t* gy,
                                     int16_t* gu, int16_t* gv) {
@@ -497,7 +505,10 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
 // the wave's LDS). Palette candidate (source only, so decided here in parallel rather than in the
 // reconstruction wavefront): the block's distinct luma values, its colours into the palette
 // cells, palette_rate2 into pal_rate for the RD comparison of the reconstruction. *pal_k: the
-// colour count of the candidate (0: none).
+// colour count of the candidate (0: none) in the low nibble; with av1_chroma_palette the chroma
+// candidate's pair count in the high nibble (pairs into the pal_uv cells, rate into pal_rate_uv).
+// kUv: the session runs with av1_chroma_palette (its own kernels: without it they are what they were).
+template <bool kUv>
 __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdge& E, uint32_t* seen, uint8_t* map,
                                uint8_t* col, int* pal_k) {
     const FrameArgs& f = A.f;
@@ -557,10 +568,49 @@ __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdg
         }
         wsync();
     }
+    // Chroma palette candidate (av1_core.h palette_colors_uv): one chroma sample per lane (64 of a
+    // 16x16 block, 16 of an 8x8), its pair packed as U << 8 | V. The distinct pairs come out in
+    // (U, V) order by repeated wave minima over the pairs above the last one found: at most nine
+    // rounds, each lane learns its pair's index on the way, and the pairs stay in two packed words.
+    if (kUv && r + (1 << bsl) <= g.mi_rows && c + (1 << bsl) <= g.mi_cols) {
+        const int cn = n >> 1, m = cn * cn;
+        int key = 0x10000;
+        if (l < m) {
+            const size_t o = (size_t)(r * 2 + l / cn) * f.stride_c + c * 2 + l % cn;
+            key = ((int)f.src.u[o] << 8) | (int)f.src.v[o];
+        }
+        uint64_t U = 0, V = 0;
+        int k = 0, cur = -1, idx = 0;
+        for (int q = 0; q <= kPalMax; q++) {
+            const int mn = __builtin_amdgcn_readfirstlane(wmin(key > cur ? key : 0x10000));   // wave-uniform: scalar
+            if (mn == 0x10000) break;
+            k = q + 1;
+            if (q == kPalMax) break;   // a ninth pair: no candidate
+            if (key == mn) idx = q;
+            U |= (uint64_t)(mn >> 8) << (8 * q);
+            V |= (uint64_t)(mn & 255) << (8 * q);
+            cur = mn;
+        }
+        if (k >= 2 && k <= kPalMax) {
+            if (l < m) map[l] = (uint8_t)idx;
+            wsync();
+            int r2 = l < m ? palette_rate2_px(map, cn, l / cn, l % cn, k) : 0;
+            r2 = wsum(r2) + palette_uv_rate2_head(U, V, k);
+            const int n8 = (1 << bsl) >> 1;
+            for (int i = l; i < n8 * n8 * 16; i += 64) {
+                const int cell = i >> 4, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
+                A.pal_uv[((size_t)ry * g.c8 + cx) * 16 + (i & 15)] = (uint8_t)pal_byte(i & 8 ? V : U, i & 7);
+            }
+            if (l == 0) A.pal_rate_uv[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2;
+            *pal_k |= k << 4;
+        }
+        wsync();
+    }
     return best;
 }
 
 // Key frames: intra mode per block from the source edges (one wave per unit).
+template <bool kUv>
 __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ IntraEdge E[4];
@@ -581,9 +631,9 @@ __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
         unit_block(g, uy, ux, k, r, c);
         BlkInfo b{};
         b.bsl = (uint8_t)bsl;
-        b.mode = (uint8_t)intra_mode_wave(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
+        b.mode = (uint8_t)intra_mode_wave<kUv>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
         b.uv_mode = DC_PRED;
-        b.pad1 = (uint8_t)pal_k;   // the candidate's colour count rides in the cell until k_av1_intra_rec decides
+        b.pad1 = (uint8_t)pal_k;   // the candidates' colour counts (luma | chroma << 4) ride in the cell until k_av1_intra_rec decides
         set_cells(A, r, c, bsl, b);
         wsync();
     }
@@ -592,7 +642,8 @@ __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
 // Inter frames with av1_intra_inter: the same decision for every block whose inter coding kept
 // levels (k_av1_inter's cells: inter and not skipped), one wave per unit. The cells stay the inter
 // coding's, so the mode and the colour count travel in A.cand: bit 0 candidate, bits 8..15 the
-// mode, bits 16..19 the palette candidate's colour count.
+// mode, bits 16..19 the palette candidate's colour count, bits 20..23 the chroma palette candidate's.
+template <bool kUv>
 __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ IntraEdge E[4];
@@ -615,7 +666,7 @@ __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
         const BlkInfo b = A.blk[cell];
         int cand = 0;
         if (blk_inter(b) && !blk_skip(b)) {   // wave-uniform
-            const int mode = intra_mode_wave(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
+            const int mode = intra_mode_wave<kUv>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
             cand = 1 | (mode << 8) | (pal_k << 16);
         }
         if (lane() == 0) A.cand[cell] = cand;
@@ -628,7 +679,7 @@ __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
 // the block is worked out in LDS and becomes the block's coding - reconstruction, levels, level
 // contexts, cells - only where its J plus the mode-bits bias is below the inter coding's
 // (av1_cpu.cpp intra_trial); otherwise nothing is stored.
-template <bool kTrial>
+template <bool kTrial, bool kUv>
 __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, int r, int c, int bsl, int qidx, int cand) {
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
@@ -642,7 +693,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         b.bsl = (uint8_t)bsl;
         b.mode = (uint8_t)(cand >> 8);
         b.uv_mode = DC_PRED;
-        b.pad1 = (uint8_t)((cand >> 16) & 15);
+        b.pad1 = (uint8_t)((cand >> 16) & 255);
     } else {
         b = A.blk[cell];
     }
@@ -662,13 +713,16 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         L.pred[320 + i] = (uint8_t)dcv;
     }
     wsync();
-    uint32_t s = code_block_wave<kTrial ? 2 : 0>(L, F, log2n, qidx, true, lev_ptr(A, r, c, bsl, 0),
+    // levels in LDS until the decisions are made: a trial, or a session with chroma palettes
+    // (kUv), whose decision needs the chroma J; otherwise code_block_wave stores them
+    constexpr bool in_lds = kTrial || kUv;
+    uint32_t s = code_block_wave<in_lds ? 2 : 0>(L, F, log2n, qidx, true, lev_ptr(A, r, c, bsl, 0),
                                                  lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
     long long jreg = L.jreg;
     b.tx_type = (int16_t)((s >> 25) & 1 ? TX_IDTX : TX_DCT_DCT);
     // palette candidate from k_av1_intra_modes (colours already in the palette cells):
     // exact palette of the source luma vs the transform path (av1_cpu.cpp intra_block)
-    const int kc = b.pad1;
+    const int kc = b.pad1 & 15, kuv = kUv ? b.pad1 >> 4 : 0;
     b.pad1 = 0;
     b.pal_n = 0;
     if (kc && tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx)) < jreg) {
@@ -678,7 +732,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         b.tx_type = TX_DCT_DCT;
         int16_t* gy = lev_ptr(A, r, c, bsl, 0);
         for (int i = l; i < n * n; i += 64) {
-            if (kTrial) L.lv[i] = 0;
+            if (in_lds) L.lv[i] = 0;
             else gy[i] = 0;
             L.pred[i] = L.src[i];
         }
@@ -686,9 +740,26 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         s = (s & ~(1u << 24)) | ((s & 0xffff00u) ? (1u << 24) : 0u);
         wsync();
     }
+    // chroma palette candidate (av1_chroma_palette): the exact pairs of the source chroma vs both
+    // DCT planes (av1_cpu.cpp intra_code)
+    long long jchr = kTrial ? L.jchr : 0;
+    if (kUv && kuv && tx_rd_cost(0, A.pal_rate_uv[cell], ac_q(qidx)) < L.jchr) {   // kuv: levels in LDS
+        jchr = tx_rd_cost(0, A.pal_rate_uv[cell], ac_q(qidx));
+        b.pal_n = (uint8_t)(b.pal_n | (kuv << 4));
+        for (int i = l; i < cn * cn; i += 64) {
+            L.lv[256 + i] = L.lv[320 + i] = 0;
+            L.pred[256 + i] = L.src[256 + i];
+            L.pred[320 + i] = L.src[320 + i];
+        }
+        s &= ~0xffff00u;   // no chroma levels: the summary and the skip flag come from luma
+        s = (s & ~(1u << 24)) | ((s & 0xffu) ? (1u << 24) : 0u);
+        wsync();
+    }
     if (kTrial) {
         // wave-uniform: every lane reads the same words
-        if (!(jreg + L.jchr + tx_rd_cost(0, kIntraInterBias2, ac_q(qidx)) < A.jinter[cell])) return;
+        if (!(jreg + jchr + tx_rd_cost(0, kIntraInterBias2, ac_q(qidx)) < A.jinter[cell])) return;
+    }
+    if (in_lds) {
         for (int p = 0; p < 3; p++) {
             int16_t* gp = lev_ptr(A, r, c, bsl, p);
             const int m = p ? cn * cn : n * n, o = p == 0 ? 0 : (p == 1 ? 256 : 320);
@@ -706,6 +777,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
 }
 
 // Key frames: one workgroup (16 waves) per tile; unit (x, y) of the tile at step x + y.
+template <bool kUv>
 __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[16];
@@ -731,7 +803,7 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
             for (int k = 0; k < nb; k++) {
                 int r, c;
                 unit_block(g, uy0 + y, ux0 + x, k, r, c);
-                intra_rec_block<false>(A, Lw[w], F, r, c, bsl, qidx, -1);
+                intra_rec_block<false, kUv>(A, Lw[w], F, r, c, bsl, qidx, -1);
             }
         }
         __syncthreads();
@@ -744,6 +816,7 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
 // as it stands (an inter neighbour's is final, a candidate neighbour's was decided at an earlier
 // step). A tile without candidates returns before loading anything; a unit without one costs
 // its wave nothing but the step's barrier.
+template <bool kUv>
 __global__ __launch_bounds__(1024) void k_av1_inter_intra(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[16];
@@ -773,7 +846,7 @@ __global__ __launch_bounds__(1024) void k_av1_inter_intra(Av1Args A) {
                 int r, c;
                 unit_block(g, uy0 + y, ux0 + x, k, r, c);
                 const int cand = A.cand[(size_t)(r >> 1) * g.c8 + (c >> 1)];
-                if (cand & 1) intra_rec_block<true>(A, Lw[w], F, r, c, bsl, qidx, cand);
+                if (cand & 1) intra_rec_block<true, kUv>(A, Lw[w], F, r, c, bsl, qidx, cand);
             }
         }
         __syncthreads();
@@ -1174,7 +1247,7 @@ __device__ __forceinline__ int code_coeffs(WaveTokenSink& w, const CdfContext& c
 // Lane-parallel palette_tokens (codec/av1_core.h code_palette_tokens): every sample's
 // colour context depends only on the index map, so lanes rank their samples at once and
 // store each token at its anti-diagonal position.
-__device__ void code_palette_tokens(WaveTokenSink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl,
+__device__ __forceinline__ void code_palette_tokens(WaveTokenSink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl,
                                     int k) {
     const int l = lane(), n = 4 << bsl;
     const uint8_t* col = v.pal_at(r, c);
@@ -1200,6 +1273,36 @@ __device__ void code_palette_tokens(WaveTokenSink& w, const CdfContext& cx, cons
     wsync();
 }
 
+// The chroma map of palette_tokens (codec/av1_core.h code_palette_tokens_uv), one sample per lane:
+// 64 of a 16x16 block, 16 of an 8x8.
+__device__ __forceinline__ void code_palette_tokens_uv(WaveTokenSink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl,
+                                       int k) {
+    const int l = lane(), n = 2 << bsl, m = n * n;
+    const uint8_t* cuv = v.pal_uv_at(r, c);
+    const uint64_t U = pal_load8(cuv), V = pal_load8(cuv + 8);
+    uint8_t* map = (uint8_t*)w.bits;   // the wave's LDS bit buffer, unused here
+    if (l < m) {
+        const size_t o = (size_t)(r * 2 + l / n) * v.stride_c + c * 2 + l % n;
+        map[l] = (uint8_t)palette_index_uv(U, V, k, v.src_u[o], v.src_v[o]);
+    }
+    wsync();
+    code_ns(w, k, map[0]);
+    w.flush();
+    if (l > 0 && l < m) {
+        const int y = l / n, x = l % n, d = x + y;
+        const int before = d < n ? d * (d + 1) / 2 : n * n - (2 * n - 1 - d) * (2 * n - d) / 2;
+        const int jmax = d < n ? d : n - 1;
+        const int o = w.n + before + (jmax - x) - 1;
+        uint32_t order;
+        const int ctx = palette_color_context(map, n, y, x, k, &order);
+        if (o < w.cap) w.p[o] = tok_sym(cdf_off(cx, cx.palette_uv_color[k - 2][ctx]), k, palette_rank(order, k, map[l]));
+    }
+    w.n += m - 1;
+    wsync();
+}
+
+// kUv: the session runs with av1_chroma_palette (code_unit's chroma palette syntax compiled in).
+template <bool kUv>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_av1_tokens(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ uint32_t bits_w[4][256];
@@ -1225,10 +1328,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     v.pal = A.pal;
     v.src_y = f.src.y;
     v.stride_y = f.stride_y;
+    v.pal_uv = A.pal_uv;
+    v.src_u = f.src.u;
+    v.src_v = f.src.v;
+    v.stride_c = f.stride_c;
     const int ux = u % f.mb_w, uy = u / f.mb_w;
     WaveTokenSink sink{A.tok + (size_t)u * kTokCap, 0, kTokCap, 0u, 0, bits_w[w]};
     const TileRect t = tile_of(g, uy * 4, ux * 4);
-    code_unit(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
+    code_unit<WaveTokenSink, kUv>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
     sink.flush();
     if (lane() == 0) A.tok_n[u] = sink.n;
 }
@@ -1906,14 +2013,27 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     const int n = a.f.mb_w * a.f.mb_h;
     const int tiles = a.geo.tile_cols * a.geo.tile_rows;
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_av1_intra_modes, dim3((n + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_av1_intra_rec, dim3(tiles), dim3(1024), 0, s, a);
+    // av1_chroma_palette: the kernels with the chroma candidate, decision and syntax in place of
+    // the ones without (the same launches either way)
+    const bool uv = a.chroma_palette != 0;
+    if (uv) {
+        hipLaunchKernelGGL(k_av1_intra_modes<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_av1_intra_rec<true>, dim3(tiles), dim3(1024), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(k_av1_intra_modes<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_av1_intra_rec<false>, dim3(tiles), dim3(1024), 0, s, a);
+    }
     const bool ltr_on = a.f.ltr_cfg.mode == ltr::LTR_BUFMAP;
     if (a.intra_inter) {   // av1_intra_inter: the inter coding with its J, then the candidates as intra blocks
         if (ltr_on) hipLaunchKernelGGL((k_av1_inter<true, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_av1_inter<false, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_av1_cand_modes, dim3((n + 3) / 4), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_av1_inter_intra, dim3(tiles), dim3(1024), 0, s, a);
+        if (uv) {
+            hipLaunchKernelGGL(k_av1_cand_modes<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_av1_inter_intra<true>, dim3(tiles), dim3(1024), 0, s, a);
+        } else {
+            hipLaunchKernelGGL(k_av1_cand_modes<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_av1_inter_intra<false>, dim3(tiles), dim3(1024), 0, s, a);
+        }
     } else if (ltr_on) {
         hipLaunchKernelGGL((k_av1_inter<true, false>), dim3((n + 3) / 4), dim3(256), 0, s, a);
     } else {
@@ -1921,7 +2041,8 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     }
     hipLaunchKernelGGL(k_av1_merge, dim3(a.geo.sb_cols * a.geo.sb_rows), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_av1_modes, dim3((a.geo.c8 * a.geo.r8 + 255) / 256), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_av1_tokens, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    if (uv) hipLaunchKernelGGL(k_av1_tokens<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_av1_tokens<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_tok_scan, dim3(tiles), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_tok_copy, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_cdf, dim3(tiles * kEcParts), dim3(64), 0, s, a);

@@ -36,7 +36,7 @@ class SkH264Config(ctypes.Structure):
         ("subpel", ctypes.c_int32), ("intra4x4", ctypes.c_int32),
         ("tile_cols_log2", ctypes.c_int32), ("tile_rows_log2", ctypes.c_int32),
         ("rc_mode", ctypes.c_int32), ("bitrate_kbps", ctypes.c_int32), ("ltr_slots", ctypes.c_int32),
-        ("av1_intra_inter", ctypes.c_int32),
+        ("av1_intra_inter", ctypes.c_int32), ("av1_chroma_palette", ctypes.c_int32),
     ]
 
 
@@ -71,7 +71,7 @@ class SkCaptureSettings(ctypes.Structure):
         ("h264_aq_strength", ctypes.c_int32), ("h264_subpel", ctypes.c_int32), ("h264_intra4x4", ctypes.c_int32),
         ("h264_rc_mode", ctypes.c_int32), ("h264_bitrate_kbps", ctypes.c_int32),
         ("h264_me_full", ctypes.c_int32), ("h264_ltr_slots", ctypes.c_int32),
-        ("av1_intra_inter", ctypes.c_int32),
+        ("av1_intra_inter", ctypes.c_int32), ("av1_chroma_palette", ctypes.c_int32),
     ]
 
 
@@ -342,8 +342,9 @@ class H264Encoder:
                  src_width: int = 0, src_height: int = 0, num_refs: int = 1, codec: str = "h264",
                  aq_strength: float = 0.0, subpel: bool = True, intra4x4: bool = False,
                  tile_cols_log2: int = -1, tile_rows_log2: int = -1, rate_control: str = "cqp",
-                 bitrate_kbps: int = 0, ltr_slots: int = 0, av1_intra_inter: bool = False):
-        """av1_intra_inter: AV1 only (Av1Encoder(intra_inter=...)), the other codecs ignore it. ltr_slots: long-term reference cache, pictures kept per stream (stripe, or the picture in
+                 bitrate_kbps: int = 0, ltr_slots: int = 0, av1_intra_inter: bool = False,
+                 av1_chroma_palette: bool = False):
+        """av1_intra_inter, av1_chroma_palette: AV1 only (Av1Encoder(intra_inter=..., chroma_palette=...)), the other codecs ignore them. ltr_slots: long-term reference cache, pictures kept per stream (stripe, or the picture in
         full-frame mode) for content that comes back, 0 = off, 1..8 (AV1: 1..7); H.264: not with
         num_refs > 1. aq_strength: MB-level adaptive QP (h264_mb.h aq_offset), 1.0 = x264 aq-mode 1
         strength; 0 = constant QP per slice (x264 ultrafast behaviour). deblock: True / False,
@@ -362,7 +363,8 @@ class H264Encoder:
                                 int(round(aq_strength * 16)), 0 if subpel else -1, 1 if intra4x4 else 0,
                                 int(tile_cols_log2), int(tile_rows_log2),
                                 RC_MODES[rate_control], int(bitrate_kbps), int(ltr_slots),
-                                1 if av1_intra_inter and codec == "av1" else 0)
+                                1 if av1_intra_inter and codec == "av1" else 0,
+                                1 if av1_chroma_palette and codec == "av1" else 0)
         if codec not in ("h264", "hevc", "av1"):
             raise ValueError("codec must be 'h264', 'hevc' or 'av1'")
         self.codec = codec
@@ -634,12 +636,20 @@ class Av1Encoder(H264Encoder):
     2..8 colours) and keeps the cheaper coding by RD cost: new content (a window that opens, text
     that scrolls in) is no longer coded as a residual against an unrelated picture. Inter frames
     then set `allow_screen_content_tools`. Off (the default), every byte is what it was without
-    the option; it combines with ltr_slots and every rate mode."""
+    the option; it combines with ltr_slots and every rate mode.
 
-    def __init__(self, width: int, height: int, *, intra_inter: bool = False, **kw):
+    chroma_palette = True lets every intra block that may carry a luma palette (all blocks of key
+    frames; with intra_inter the intra blocks of inter frames) code its chroma as an exact palette
+    of 2..8 (U, V) pairs with one index map for both planes, where that costs less by RD than
+    UV_DC_PRED + DCT: coloured text, selections and icons reconstruct without ringing. Off (the
+    default), every byte is what it was without the option."""
+
+    def __init__(self, width: int, height: int, *, intra_inter: bool = False, chroma_palette: bool = False, **kw):
         kw.pop("fullframe", None)
         kw.pop("av1_intra_inter", None)
-        super().__init__(width, height, codec="av1", fullframe=True, av1_intra_inter=bool(intra_inter), **kw)
+        kw.pop("av1_chroma_palette", None)
+        super().__init__(width, height, codec="av1", fullframe=True, av1_intra_inter=bool(intra_inter),
+                         av1_chroma_palette=bool(chroma_palette), **kw)
 
 
 class JpegEncoder(H264Encoder):

@@ -202,6 +202,10 @@ def main():
     put("palette_y_size", img.aom_table([7952, 13000, 18149, 21478, 25527, 29241], 7, 8, 7), [7], 8)
     put("palette_y_color", img.aom_table([[28710], [16384], [10553], [27036], [31603]], 35, 9,
                                          [n for n in range(2, 9) for _ in range(5)]), [7, 5], 9)
+    # chroma palettes (av1_chroma_palette): the uv size CDF [7] and the uv colour-index CDFs, same layouts
+    put("palette_uv_size", img.aom_table([8713, 19979, 27128, 29609, 31331, 32272], 7, 8, 7), [7], 8)
+    put("palette_uv_color", img.aom_table([[29089], [16384], [8713], [29257], [31610]], 35, 9,
+                                          [n for n in range(2, 9) for _ in range(5)]), [7, 5], 9)
     # ---- motion vectors (libaom nmv_context: joints, then two nmv_component structs)
     mv = img.aom_struct([4096, 11264, 19328], [(1, 4), (1, 11), (2, 4), (1, 4), (1, 2), (1, 2), (1, 2), (1, 2), (10, 2),
                                                (1, 11), (2, 4), (1, 4), (1, 2), (1, 2), (1, 2), (1, 2), (10, 2)])
@@ -269,8 +273,10 @@ def main():
     w("")
     w("namespace sk::av1 {")
     w("")
+    # tables added after the first layout go behind the coefficient part: every earlier CDF keeps its offset
+    tail_names = ["palette_uv_size", "palette_uv_color"]
     mode_names = [k for k in T if k not in ("txb_skip", "eob_extra", "dc_sign", "coeff_base_eob", "coeff_base",
-                                            "coeff_br") and not k.startswith("eob_pt")]
+                                            "coeff_br") and not k.startswith("eob_pt") and k not in tail_names]
     coef_names = ["txb_skip", "eob_extra", "dc_sign", "eob_pt_16", "eob_pt_32", "eob_pt_64", "eob_pt_128",
                   "eob_pt_256", "eob_pt_512", "eob_pt_1024", "coeff_base_eob", "coeff_base", "coeff_br"]
     # one CdfContext = mode part + the coefficient part of one quantizer context
@@ -283,6 +289,10 @@ def main():
     for k in coef_names:
         cdfs, dims, width = T[k]
         d = "".join(f"[{x}]" for x in dims[1:])
+        w(f"    uint16_t {k}{d}[{width}];")
+    for k in tail_names:
+        cdfs, dims, width = T[k]
+        d = "".join(f"[{x}]" for x in dims)
         w(f"    uint16_t {k}{d}[{width}];")
     w("};")
     w("")
@@ -298,6 +308,9 @@ def main():
             cdfs, dims, width = T[k]
             per = len(cdfs) // 4
             parts.append(nest([fmt_cdf(c, width) for c in cdfs[q * per:(q + 1) * per]], dims[1:]))
+        for k in tail_names:
+            cdfs, dims, width = T[k]
+            parts.append(nest([fmt_cdf(c, width) for c in cdfs], dims))
         w("    {" + ",\n     ".join(parts) + "},")
     w("};")
     w("")
