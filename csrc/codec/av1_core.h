@@ -17,8 +17,10 @@
 //   screen-content identity transform, chosen per luma block); intra DC / V / H /
 //   SMOOTH(_V/_H) / PAETH / directional, luma palettes of 2..8 colours
 //   (code_palette_mode_info / code_palette_tokens) and, with av1_chroma_palette, exact chroma
-//   palettes of 2..8 (U, V) pairs on the same blocks (chroma is UV_DC_PRED + DCT_DCT otherwise);
-//   no filter-intra / CfL / intraBC, intra edge filter off; one reference per block (LAST, or LAST2 for
+//   palettes of 2..8 (U, V) pairs on the same blocks and, with av1_cfl, chroma from luma
+//   (UV_CFL_PRED, §7.11.5: cfl_predict / code_cfl_alphas) on any intra block; chroma is UV_DC_PRED
+//   otherwise, and DCT_DCT always (the only other UV mode whose implied transform is DCT_DCT is CfL);
+//   no filter-intra / intraBC, intra edge filter off; one reference per block (LAST, or LAST2 for
 //   the cached picture of ltr.h), single prediction, EIGHTTAP regular filter, quarter-pel
 //   vectors (allow_high_precision_mv = 0); no order hints (no temporal MVs, no skip mode);
 //   in-loop deblocking (av1_lf.h) and CDEF (av1_cdef.h) on, loop restoration off.
@@ -84,7 +86,9 @@ struct BlkInfo {
     uint8_t mode;      // YMode (intra 0..12, inter NEARESTMV..NEWMV)
     uint8_t uv_mode;   // UVMode (intra)
     uint8_t flags;     // bit0 is_inter, bit1 skip, bit2 merged-static (encoder), bits 4-5 RefMvIdx
-    int16_t mv_row, mv_col;   // 1/8 pel (LAST), even values (no high-precision MVs)
+    int16_t mv_row, mv_col;   // 1/8 pel (LAST), even values (no high-precision MVs); an intra cell with UV_CFL_PRED:
+                              // CflAlphaU / CflAlphaV, -16..16 (cfl_alpha_u / cfl_alpha_v; every reader of a
+                              // neighbour's vector asks blk_inter first), 0 in every other intra cell
     int16_t tx_type;   // luma transform type: TX_DCT_DCT (0) or TX_IDTX (1); inter chroma follows it
     uint8_t pal_n;     // low nibble PaletteSizeY, high nibble PaletteSizeUV (0: no palette; colours in the frame's
                        // palette cells); read through pal_ny / pal_nuv
@@ -95,6 +99,8 @@ SK_HD bool blk_inter(const BlkInfo& b) { return (b.flags & 1) != 0; }
 SK_HD bool blk_skip(const BlkInfo& b) { return (b.flags & 2) != 0; }
 SK_HD int pal_ny(const BlkInfo& b) { return b.pal_n & 15; }
 SK_HD int pal_nuv(const BlkInfo& b) { return b.pal_n >> 4; }
+SK_HD int cfl_alpha_u(const BlkInfo& b) { return b.mv_row; }
+SK_HD int cfl_alpha_v(const BlkInfo& b) { return b.mv_col; }
 
 // ---------------------------------------------------------------------------------
 // Transforms. Forward: encoder choice, an integer DCT-II scaled to 8x the
@@ -1495,6 +1501,52 @@ SK_HD int palette_rate2_px(const uint8_t* map, int n, int i, int j, int k) {
     return rep ? 1 : 2 + 2 * ceil_log2(k);
 }
 
+// ---------------------------------------------------------------------------------
+// Chroma from luma (av1_cfl; §7.11.5 predict_chroma_from_luma, §5.11.45 read_cfl_alphas) on the
+// cn x cn chroma block (cn = 4 or 8) of an intra block: L = (sum of the 2x2 reconstructed luma
+// samples) << 1, ac = L - Round2(sum L, 2 log2 cn), pred = Clip1(dc + Round2Signed(alpha * ac, 6))
+// with dc the plane's DC_PRED value and alpha in -16..16 per plane. Every block here has one luma
+// transform that covers it, so the whole block counts as available luma, also where an 8x8 block
+// hangs over the picture edge. The chroma transform stays DCT_DCT (Mode_To_Txfm[UV_CFL_PRED]).
+// Encoder choice (av1_cpu.cpp intra_code = intra_rec_block of the kernels): after UV_DC_PRED and
+// the chroma palette, a block whose DC coding kept a chroma level and whose ac is not all zero
+// searches one alpha per plane (cfl_alpha0 from the least-squares fit, then the exact SSE of 0, a0
+// and a0 one step further from zero: cfl_cand) and takes CfL where the J of both planes plus
+// cfl_rate2 is below the chroma J standing.
+SK_HD int cfl_luma(const uint8_t* y, int pitch, int i, int j) {
+    const uint8_t* p = y + 2 * i * pitch + 2 * j;
+    return (p[0] + p[1] + p[pitch] + p[pitch + 1]) << 1;
+}
+SK_HD int cfl_avg(int sum, int cl2) { return (sum + (1 << (2 * cl2 - 1))) >> (2 * cl2); }
+SK_HD int cfl_px(int dc, int alpha, int ac) {
+    const int x = alpha * ac;
+    return sk_clip255(dc + (x < 0 ? -((32 - x) >> 6) : (x + 32) >> 6));
+}
+// clamp(trunc(64 sxy / sxx), -16, 16) for sxx > 0, without a division
+SK_HD int cfl_alpha0(long long sxx, long long sxy) {
+    const long long m = 64 * (sxy < 0 ? -sxy : sxy);
+    int a = 0;
+    for (int k = 1; k <= 16; k++) a += k * sxx <= m ? 1 : 0;
+    return sxy < 0 ? -a : a;
+}
+// The k-th alpha tried (ascending magnitude: the first of equal SSEs wins): 0, a0, a0 one step further.
+SK_HD int cfl_cand(int a0, long long sxy, int k) {
+    const int further = sk_clip(a0 + (sxy < 0 ? -1 : (sxy > 0 ? 1 : 0)), -16, 16);
+    return k == 0 ? 0 : (k == 1 ? a0 : further);
+}
+// Static rate estimate (half bits): 3 bits for UV_CFL_PRED above UV_DC_PRED, 3 for the joint sign,
+// 4 per coded magnitude.
+SK_HD int cfl_rate2(int alpha_u, int alpha_v) { return 2 * (3 + 3 + (alpha_u ? 4 : 0) + (alpha_v ? 4 : 0)); }
+// cfl_alpha_signs (ZERO 0, NEG 1, POS 2 per plane; both ZERO cannot be coded), cfl_alpha_u, cfl_alpha_v
+template <class Sink>
+SK_HD void code_cfl_alphas(Sink& w, const CdfContext& cx, const BlkInfo& b) {
+    const int au = cfl_alpha_u(b), av = cfl_alpha_v(b);
+    const int su = au == 0 ? 0 : (au < 0 ? 1 : 2), sv = av == 0 ? 0 : (av < 0 ? 1 : 2);
+    w.sym(cdf_off(cx, cx.cfl_sign), 8, 3 * su + sv - 1);
+    if (su) w.sym(cdf_off(cx, cx.cfl_alpha[(su - 1) * 3 + sv]), 16, (au < 0 ? -au : au) - 1);
+    if (sv) w.sym(cdf_off(cx, cx.cfl_alpha[(sv - 1) * 3 + su]), 16, (av < 0 ? -av : av) - 1);
+}
+
 // Is the block containing mi (mr, mc) before the block at (r, c) in coding order?
 // (raster superblocks, recursive quad-split Z order inside each 64x64 superblock)
 SK_HD uint32_t zorder16(int r, int c) {
@@ -1513,8 +1565,9 @@ struct DecodedBefore {
     SK_HD bool operator()(int mr, int mc) const { return decoded_before(mr, mc, r, c); }
 };
 
-// Mode info + residual of one block (§5.11.5 decode_block).
-template <class Sink, bool kUv = true>
+// Mode info + residual of one block (§5.11.5 decode_block). kCfl = false compiles the CfL alphas'
+// syntax out, as kUv does the chroma palette's: the GPU token kernel of sessions without av1_cfl.
+template <class Sink, bool kUv = true, bool kCfl = true>
 SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int r, int c, int bsl) {
     const BlkInfo& b = v.at(r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
@@ -1527,6 +1580,7 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
         if (bsl <= 3) w.sym(cdf_off(cx, cx.uv_mode_cfl_allowed[b.mode]), 14, b.uv_mode);
         else w.sym(cdf_off(cx, cx.uv_mode_cfl_not_allowed[b.mode]), 13, b.uv_mode);
         if (is_directional(b.uv_mode)) w.sym(cdf_off(cx, cx.angle_delta[b.uv_mode - V_PRED]), 7, 3);
+        if (kCfl && b.uv_mode == UV_CFL_PRED) code_cfl_alphas(w, cx, b);
         if (v.screen) code_palette_mode_info<Sink, kUv>(w, cx, v, t, r, c, bsl, b);
     } else {
         // is_inter (§8.3.2): an unavailable neighbour counts as inter; both available: 3 if both
@@ -1543,6 +1597,7 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
         if (bsl <= 3) w.sym(cdf_off(cx, cx.uv_mode_cfl_allowed[b.mode]), 14, b.uv_mode);
         else w.sym(cdf_off(cx, cx.uv_mode_cfl_not_allowed[b.mode]), 13, b.uv_mode);
         if (is_directional(b.uv_mode)) w.sym(cdf_off(cx, cx.angle_delta[b.uv_mode - V_PRED]), 7, 3);
+        if (kCfl && b.uv_mode == UV_CFL_PRED) code_cfl_alphas(w, cx, b);
         if (v.screen) code_palette_mode_info<Sink, kUv>(w, cx, v, t, r, c, bsl, b);
     } else if (!v.key) {
         // single_ref contexts (§8.3.2 count_refs): only neighbours that are inter count. All
@@ -1615,7 +1670,7 @@ SK_HD bool code_partition_symbol(Sink& w, const CdfContext& cx, const FrameView&
 // partition symbols of the 64 / 32 nodes it opens, then its own block(s); a unit
 // inside a larger (merged) block contributes nothing. Units in Z order within
 // raster superblocks reproduce decode_partition's order exactly.
-template <class Sink, bool kUv = true>
+template <class Sink, bool kUv = true, bool kCfl = true>
 SK_HD void code_unit(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int ux, int uy) {
     const int r = uy * 4, c = ux * 4;
     if (r >= v.geo.mi_rows || c >= v.geo.mi_cols) return;
@@ -1627,19 +1682,19 @@ SK_HD void code_unit(Sink& w, const CdfContext& cx, const FrameView& v, const Ti
             continue;
         }
         if (code_partition_symbol(w, cx, v, t, r, c, L)) {
-            code_block<Sink, kUv>(w, cx, v, t, r, c, L);
+            code_block<Sink, kUv, kCfl>(w, cx, v, t, r, c, L);
             return;
         }
     }
     if (code_partition_symbol(w, cx, v, t, r, c, 2)) {
-        code_block<Sink, kUv>(w, cx, v, t, r, c, 2);
+        code_block<Sink, kUv, kCfl>(w, cx, v, t, r, c, 2);
         return;
     }
     for (int q = 0; q < 4; q++) {
         const int rr = r + (q >> 1) * 2, cc = c + (q & 1) * 2;
         if (rr >= v.geo.mi_rows || cc >= v.geo.mi_cols) continue;
         code_partition_symbol(w, cx, v, t, rr, cc, 1);
-        code_block<Sink, kUv>(w, cx, v, t, rr, cc, 1);
+        code_block<Sink, kUv, kCfl>(w, cx, v, t, rr, cc, 1);
     }
 }
 

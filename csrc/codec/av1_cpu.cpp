@@ -204,6 +204,7 @@ CpuAv1Encoder::CpuAv1Encoder(const h264::EncoderConfig& cfg, int tcl, int trl) :
     pal.assign((size_t)geo.c8 * geo.r8 * 8, 0);
     pal_uv.assign((size_t)geo.c8 * geo.r8 * 16, 0);
     chroma_palette = cfg.av1_chroma_palette > 0;
+    cfl = cfg.av1_cfl > 0;
     jinter.assign((size_t)geo.c8 * geo.r8, 0);
     intra_inter = cfg.av1_intra_inter > 0;
     lctx_h[1] = lctx_h[2] = geo.mi_rows >> 1;
@@ -348,7 +349,7 @@ int intra_mode_decision(const uint8_t* src, int stride, int x, int y, int log2n,
 // One intra block in `mode` (the open-loop decision), predicted from the reconstruction of its
 // neighbours as it stands: levels, reconstruction and the J of the coding (luma: the cheapest of
 // DCT_DCT, IDTX and the exact palette; chroma: UV_DC_PRED, DCT_DCT, or with av1_chroma_palette the
-// exact palette where that is cheaper) into `o`. Changes no state.
+// exact palette, or with av1_cfl UV_CFL_PRED, DCT_DCT, where that is cheaper) into `o`. Changes no state.
 void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const {
     const h264::Geometry& g = fe.g;
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
@@ -393,8 +394,8 @@ void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mod
         }
     }
     bool nz = recon_block(ly, log2n, fp.qidx, true, b.tx_type, py, o.rec, n);
-    // chroma: UV_DC_PRED. Every other UV mode implies an ADST-family chroma transform
-    // (Mode_To_Txfm, §7.13.3 compute_tx_type); this encoder's transforms are DCT_DCT.
+    // chroma: UV_DC_PRED first. Every other UV mode but UV_CFL_PRED (below) implies an ADST-family
+    // chroma transform (Mode_To_Txfm, §7.13.3 compute_tx_type); this encoder's transforms are DCT_DCT.
     const int cl2 = log2n - 1, cn = n >> 1, cx = x >> 1, cy = y >> 1;
     IntraEdge eu, ev;
     intra_edges(fe.rec[1].data(), g.stride_c, cx, cy, cn, au, al, geo.mi_cols * 2 - 1, geo.mi_rows * 2 - 1, eu);
@@ -406,6 +407,7 @@ void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mod
     int16_t* lvv = o.lev + 320;
     o.jc = quant_block(&fe.src[1][(size_t)cy * g.stride_c + cx], g.stride_c, bu, cl2, fp.qidx, true, TX_DCT_DCT, lu);
     o.jc += quant_block(&fe.src[2][(size_t)cy * g.stride_c + cx], g.stride_c, bv, cl2, fp.qidx, true, TX_DCT_DCT, lvv);
+    const bool dc_kept = any_nonzero(lu, cn * cn) || any_nonzero(lvv, cn * cn);   // before a palette clears them
     // chroma palette (av1_chroma_palette): the exact (U, V) pairs of the source vs both DCT planes
     const uint8_t* su = &fe.src[1][(size_t)cy * g.stride_c + cx];
     const uint8_t* sv = &fe.src[2][(size_t)cy * g.stride_c + cx];
@@ -428,6 +430,64 @@ void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mod
             for (int i = 0; i < cn; i++) {
                 memcpy(&bu[i * cn], su + (size_t)i * g.stride_c, (size_t)cn);
                 memcpy(&bv[i * cn], sv + (size_t)i * g.stride_c, (size_t)cn);
+            }
+        }
+    }
+    // chroma from luma (av1_cfl, av1_core.h): candidates kept a chroma level under UV_DC_PRED and have
+    // luma that varies; one alpha per plane, both planes coded again, against the chroma J standing
+    if (cfl && dc_kept) {
+        int ac[64], sum = 0;
+        bool flat = true;
+        for (int i = 0; i < cn; i++)
+            for (int j = 0; j < cn; j++) sum += ac[i * cn + j] = cfl_luma(o.rec, n, i, j);
+        const int avg = cfl_avg(sum, cl2);
+        for (int k = 0; k < cn * cn; k++) flat &= (ac[k] -= avg) == 0;
+        if (!flat) {
+            const uint8_t* sp[2] = {su, sv};
+            const int dc[2] = {intra_dc(eu, cl2), intra_dc(ev, cl2)};
+            int alpha[2];
+            long long sxx = 0;
+            for (int k = 0; k < cn * cn; k++) sxx += (long long)ac[k] * ac[k];
+            for (int p = 0; p < 2; p++) {
+                long long sxy = 0;
+                for (int i = 0; i < cn; i++)
+                    for (int j = 0; j < cn; j++) sxy += (long long)ac[i * cn + j] * ((int)sp[p][(size_t)i * g.stride_c + j] - dc[p]);
+                const int a0 = cfl_alpha0(sxx, sxy);
+                int best = 0x7fffffff;
+                alpha[p] = 0;
+                for (int q = 0; q < 3; q++) {
+                    const int a = cfl_cand(a0, sxy, q);
+                    int sse = 0;
+                    for (int i = 0; i < cn; i++)
+                        for (int j = 0; j < cn; j++) {
+                            const int e = (int)sp[p][(size_t)i * g.stride_c + j] - cfl_px(dc[p], a, ac[i * cn + j]);
+                            sse += e * e;
+                        }
+                    if (sse < best) {
+                        best = sse;
+                        alpha[p] = a;
+                    }
+                }
+            }
+            if (alpha[0] || alpha[1]) {
+                uint8_t pc[2][64];
+                int16_t lc[2][64];
+                long long j = tx_rd_cost(0, cfl_rate2(alpha[0], alpha[1]), ac_q(fp.qidx));
+                for (int p = 0; p < 2; p++) {
+                    for (int k = 0; k < cn * cn; k++) pc[p][k] = (uint8_t)cfl_px(dc[p], alpha[p], ac[k]);
+                    j += quant_block(sp[p], g.stride_c, pc[p], cl2, fp.qidx, true, TX_DCT_DCT, lc[p]);
+                }
+                if (j < o.jc) {
+                    o.jc = j;
+                    b.uv_mode = UV_CFL_PRED;
+                    b.pal_n &= 15;
+                    b.mv_row = (int16_t)alpha[0];
+                    b.mv_col = (int16_t)alpha[1];
+                    memcpy(bu, pc[0], (size_t)cn * cn);
+                    memcpy(bv, pc[1], (size_t)cn * cn);
+                    memcpy(lu, lc[0], sizeof(int16_t) * cn * cn);
+                    memcpy(lvv, lc[1], sizeof(int16_t) * cn * cn);
+                }
             }
         }
     }

@@ -121,6 +121,7 @@ class CpuAv1Encoder {
     bool palette_on = palette_enabled();
     bool intra_inter = false;        // EncoderConfig::av1_intra_inter
     bool chroma_palette = false;     // EncoderConfig::av1_chroma_palette (acts where palettes do: fp.screen)
+    bool cfl = false;                // EncoderConfig::av1_cfl (acts on every intra block)
     std::vector<long long> jinter;   // c8 * r8: J of the inter coding of the block at that origin cell (inter_block)
     int lctx_w[3] = {0, 0, 0}, lctx_h[3] = {0, 0, 0};
     int level_idx = 8;

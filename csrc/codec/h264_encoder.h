@@ -66,6 +66,9 @@ struct EncoderConfig {
                                  // intra blocks (luma palettes included, av1_core.h); the other codecs ignore it
     int av1_chroma_palette = 0;  // AV1: exact chroma palettes of 2..8 (U, V) pairs on intra blocks, where luma palettes may
                                  // occur (key frames; inter frames with av1_intra_inter); the other codecs ignore it
+    int av1_cfl = 0;             // AV1: chroma from luma (UV_CFL_PRED) on intra blocks, where it costs less by RD than the
+                                 // chroma coding standing (key frames; inter frames with av1_intra_inter); the other
+                                 // codecs ignore it
 };
 
 // Long-term cache slots in force (the three codecs share this configuration and the front end).

@@ -13,7 +13,7 @@ namespace av1 {
 namespace gpu {
 
 constexpr int kLevPerUnit = 384;
-constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2815, below)
+constexpr int kTokCap = 4096;        // tokens per 16x16 unit slot (worst case tok_bound::kUnit = 2827, below)
 constexpr int kTileChunkCap = 1 << 20;
 
 // The most tokens code_unit (av1_core.h; k_av1_tokens) can put into one unit's slot, over every
@@ -36,6 +36,7 @@ constexpr int kPaletteBits = 16 + 8 + 2 + 7 * 8;            // cache flags, firs
 constexpr int kPaletteUvBits = kPaletteBits                 // U: cache flags, first colour, extra bits, seven deltas
                                + 1 + 8 * 8;                 // V: the delta flag, eight raw colours (delta coding only where shorter)
 constexpr int kKeyHead = 1 + 1 + 1 + 1 + 1                  // skip, y mode, angle delta, uv mode, angle delta
+                         + 1 + 1 + 1                        // cfl_alpha_signs, cfl_alpha_u, cfl_alpha_v (av1_cfl)
                          + 1 + 1                            // palette_y_mode, palette_y_size
                          + (kPaletteBits + 23) / 24 + 1     // the colours' literals (the first may join pending bits)
                          + 1                                // palette_uv_mode
@@ -58,7 +59,7 @@ constexpr int kUnit = kPartition                            // partition symbols
                       + kCoefs * (1 + 4)                    // coeff_base(_eob) + four coeff_br per level
                       + kCoefs * kCoefBits / 24;            // full literals of the sign / Golomb runs
 static_assert(kCoefBits == 24 && 256 * kCoefBits <= 256 * 32, "a 16x16 block's sign / Golomb run fits the 256-word LDS bit buffer");
-static_assert(kUnit == 2815, "tok_bound changed: update the comment on kTokCap");
+static_assert(kUnit == 2827, "tok_bound changed: update the comment on kTokCap");
 static_assert(kUnit <= kTokCap, "a unit's tokens can overflow its slot (the tokens past it are dropped)");
 }   // namespace tok_bound
 
@@ -76,6 +77,8 @@ struct Av1Args {
     int* pal_rate_uv;         // [r8][c8] rate (half bits) of the chroma palette candidate of the block at that origin
                               // cell; its pair count rides in the high nibble of BlkInfo.pad1 (key frames) or in
                               // bits 20..23 of cand (inter frames)
+    int cfl;                  // EncoderConfig::av1_cfl: chroma from luma on intra blocks (k_av1_intra_rec, k_av1_inter_intra,
+                              // k_av1_tokens; the alphas ride in an intra cell's mv_row / mv_col, av1_core.h)
     int intra_inter;          // EncoderConfig::av1_intra_inter: intra blocks in inter frames; the three below only then
     long long* jinter;        // [r8][c8] J of the inter coding of the block at that origin cell (k_av1_inter)
     int* cand;                // [r8][c8] bit 0: the block is an intra candidate (its inter coding kept levels),

@@ -160,6 +160,105 @@ __device__ int rate2_wave(const int16_t* lv, int ln) {
     return wsum(r) + tx_eob_bits2(eob);
 }
 
+// The per-plane steps of code_block_wave (and of the chroma-only recoding of av1_cfl), plane at
+// offset o of L's arrays, sz = 1 << ln.
+// forward stage 1 (columns): b[k][j] = (sum_m K[k][m] a[m][j] + 512) >> 10
+__device__ __forceinline__ void fwd_cols_plane(BlkLds& L, const FdctLds& F, int ln, int o) {
+    const int l = lane(), sz = 1 << ln;
+    const int16_t* K = fdct_k(F, ln);
+    for (int i = l; i < sz * sz; i += 64) {
+        const int k = i >> ln, j = i & (sz - 1);
+        int s = 0;
+        for (int m2 = 0; m2 < sz; m2++) s += (int)K[k * sz + m2] * L.a[o + m2 * sz + j];
+        L.b[o + i] = (s + 512) >> 10;
+    }
+}
+// forward stage 2 (rows) + quantisation: DCT levels to L.lv and, with idtx_too, IDTX levels (8 x the
+// residual, still in L.a) to L.lv2; each lane's squared coefficient errors are added to ed / ei
+__device__ __forceinline__ void fwd_rows_quant_plane(BlkLds& L, const FdctLds& F, int ln, int o, int qd, int qa, bool intra,
+                                                     bool idtx_too, long long& ed, long long& ei) {
+    const int l = lane(), sz = 1 << ln;
+    const int16_t* K = fdct_k(F, ln);
+    for (int i = l; i < sz * sz; i += 64) {
+        const int k = i >> ln, lc = i & (sz - 1);
+        // |sum| <= |t|_2 |K|_2 < 2^31 (orthonormal Q13 rows, |t| <= 8 * 255 * sqrt(N)):
+        // the 32-bit sum equals av1_core.h fwd_transform's 64-bit one
+        int s = 0;
+        for (int j = 0; j < sz; j++) s += L.b[o + k * sz + j] * (int)K[lc * sz + j];
+        const int32_t c = (s + (s >= 0 ? 4096 : 4095)) >> 13;
+        const int q = i == 0 ? qd : qa;
+        const int lv = quantize(c, q, intra);
+        L.lv[o + i] = (int16_t)lv;
+        const long long e = (long long)c - dequant(lv, q);
+        ed += e * e;
+        if (idtx_too) {
+            const int32_t ci = 8 * L.a[o + i];
+            const int li = quantize(ci, q, intra);
+            L.lv2[o + i] = (int16_t)li;
+            const long long e2 = (long long)ci - dequant(li, q);
+            ei += e2 * e2;
+        }
+    }
+}
+// dequantisation of L.lv into L.a and the plane's level summary (cul | dc << 6; 0: no level);
+// kStore: the levels go to g too
+template <bool kStore>
+__device__ __forceinline__ uint32_t dequant_plane(BlkLds& L, int ln, int o, int qd, int qa, int16_t* g) {
+    const int l = lane(), sz = 1 << ln;
+    int sum = 0, nz = 0, first = 0;
+    for (int i = l; i < sz * sz; i += 64) {
+        const int q = i == 0 ? qd : qa;
+        const int lv = L.lv[o + i];
+        if (kStore) g[i] = (int16_t)lv;
+        if (i == 0) first = lv;
+        sum += lv < 0 ? -lv : lv;
+        nz |= lv;
+        L.a[o + i] = dequant(lv, q);
+    }
+    sum = wsum(sum);
+    const bool any = __ballot(nz != 0) != 0;
+    const int lv0 = __shfl(first, 0);
+    const int dc = lv0 < 0 ? 1 : (lv0 > 0 ? 2 : 0);
+    return any ? (uint32_t)(sk_min(sum, 63) | (dc << 6)) : 0u;
+}
+// inverse transform, one lane per row i (L.a -> L.b), then one lane per column j (L.b added to L.pred)
+__device__ __forceinline__ void inv_rows_lane(BlkLds& L, int ln, int o, int i, bool identity) {
+    const int sz = 1 << ln, rs = ln == 2 ? 0 : (ln == 3 ? 1 : 2);
+    int32_t t[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) t[j] = j < sz ? L.a[o + i * sz + j] : 0;
+    if (identity)
+#pragma unroll
+        for (int j = 0; j < 16; j++) t[j] = iidentity(t[j], ln);
+    else if (ln == 2) idct4(t);
+    else if (ln == 3) idct8(t);
+    else idct16(t);
+#pragma unroll
+    for (int j = 0; j < 16; j++)
+        if (j < sz) {
+            const int32_t v = rs ? (t[j] + (1 << (rs - 1))) >> rs : t[j];
+            L.b[o + i * sz + j] = sk_clip(v, -32768, 32767);
+        }
+}
+__device__ __forceinline__ void inv_cols_lane(BlkLds& L, int ln, int o, int j, bool identity) {
+    const int sz = 1 << ln;
+    int32_t t[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) t[i] = i < sz ? L.b[o + i * sz + j] : 0;
+    if (identity)
+#pragma unroll
+        for (int i = 0; i < 16; i++) t[i] = iidentity(t[i], ln);
+    else if (ln == 2) idct4(t);
+    else if (ln == 3) idct8(t);
+    else idct16(t);
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+        if (i < sz) {
+            const int k = o + i * sz + j;
+            L.pred[k] = (uint8_t)sk_clip255((int)L.pred[k] + ((t[i] + 8) >> 4));
+        }
+}
+
 // Transform, quantisation and reconstruction of one block held in L (src, pred):
 // luma n = 1 << log2n, chroma n / 2. The transform type is DCT_DCT or IDTX by RD cost
 // (the CPU encoder's quant_block rule: inter blocks over the three planes, intra blocks
@@ -189,17 +288,7 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     }
     const long long jz = 256ll * wsum(e2);
     wsync();
-    // forward stage 1 (columns): b[k][j] = (sum_m K[k][m] a[m][j] + 512) >> 10
-    for (int p = 0; p < 3; p++) {
-        const int ln = p ? log2n - 1 : log2n, sz = 1 << ln, o = base(p);
-        const int16_t* K = fdct_k(F, ln);
-        for (int i = l; i < sz * sz; i += 64) {
-            const int k = i >> ln, j = i & (sz - 1);
-            int s = 0;
-            for (int m2 = 0; m2 < sz; m2++) s += (int)K[k * sz + m2] * L.a[o + m2 * sz + j];
-            L.b[o + i] = (s + 512) >> 10;
-        }
-    }
+    for (int p = 0; p < 3; p++) fwd_cols_plane(L, F, p ? log2n - 1 : log2n, base(p));
     wsync();
     // forward stage 2 (rows) + quantisation, DCT levels to L.lv and IDTX levels (8 x the
     // residual, still in L.a) to L.lv2, with both squared coefficient errors per plane
@@ -207,29 +296,9 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     long long jd = 0, ji = 0;
     const int np = intra ? 1 : 3;   // planes in the decision
     for (int p = 0; p < 3; p++) {
-        const int ln = p ? log2n - 1 : log2n, sz = 1 << ln, o = base(p);
-        const int16_t* K = fdct_k(F, ln);
+        const int ln = p ? log2n - 1 : log2n, o = base(p);
         long long ed = 0, ei = 0;
-        for (int i = l; i < sz * sz; i += 64) {
-            const int k = i >> ln, lc = i & (sz - 1);
-            // |sum| <= |t|_2 |K|_2 < 2^31 (orthonormal Q13 rows, |t| <= 8 * 255 * sqrt(N)):
-            // the 32-bit sum equals av1_core.h fwd_transform's 64-bit one
-            int s = 0;
-            for (int j = 0; j < sz; j++) s += L.b[o + k * sz + j] * (int)K[lc * sz + j];
-            const int32_t c = (s + (s >= 0 ? 4096 : 4095)) >> 13;
-            const int q = i == 0 ? qd : qa;
-            const int lv = quantize(c, q, intra);
-            L.lv[o + i] = (int16_t)lv;
-            const long long e = (long long)c - dequant(lv, q);
-            ed += e * e;
-            if (p < np) {
-                const int32_t ci = 8 * L.a[o + i];
-                const int li = quantize(ci, q, intra);
-                L.lv2[o + i] = (int16_t)li;
-                const long long e2 = (long long)ci - dequant(li, q);
-                ei += e2 * e2;
-            }
-        }
+        fwd_rows_quant_plane(L, F, ln, o, qd, qa, intra, p < np, ed, ei);
         const long long dp = wsum64(ed), ip = wsum64(ei);
         if (p < np) {
             wsync();   // the plane's levels, for the rate estimates
@@ -281,24 +350,8 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     int nzm = 0;
     uint32_t cul = 0;
     for (int p = 0; p < 3; p++) {
-        const int ln = p ? log2n - 1 : log2n, sz = 1 << ln, o = base(p);
-        int16_t* g = p == 0 ? gy : (p == 1 ? gu : gv);
-        int sum = 0, nz = 0, first = 0;
-        for (int i = l; i < sz * sz; i += 64) {
-            const int q = i == 0 ? qd : qa;
-            const int lv = L.lv[o + i];
-            if (kJ != 2) g[i] = (int16_t)lv;
-            if (i == 0) first = lv;
-            sum += lv < 0 ? -lv : lv;
-            nz |= lv;
-            L.a[o + i] = dequant(lv, q);
-        }
-        sum = wsum(sum);
-        const bool any = __ballot(nz != 0) != 0;
-        if (any) nzm |= 1 << p;
-        const int lv0 = __shfl(first, 0);
-        const int dc = lv0 < 0 ? 1 : (lv0 > 0 ? 2 : 0);
-        const uint32_t summ = any ? (uint32_t)(sk_min(sum, 63) | (dc << 6)) : 0u;
+        const uint32_t summ = dequant_plane<kJ != 2>(L, p ? log2n - 1 : log2n, base(p), qd, qa, p == 0 ? gy : (p == 1 ? gu : gv));
+        if (summ) nzm |= 1 << p;   // a plane with a level has a nonzero sum
         cul |= summ << (8 * p);
     }
     wsync();
@@ -307,51 +360,56 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     {
         const int p = l < rows_y ? 0 : (l < rows_y + rows_c ? 1 : (l < rows_y + 2 * rows_c ? 2 : 3));
         if (p < 3) {
-            const int ln = p ? log2n - 1 : log2n, sz = 1 << ln, o = base(p);
             const int i = p == 0 ? l : (p == 1 ? l - rows_y : l - rows_y - rows_c);
-            const int rs = ln == 2 ? 0 : (ln == 3 ? 1 : 2);
-            int32_t t[16];
-#pragma unroll
-            for (int j = 0; j < 16; j++) t[j] = j < sz ? L.a[o + i * sz + j] : 0;
-            if (idtx && p < np)
-#pragma unroll
-                for (int j = 0; j < 16; j++) t[j] = iidentity(t[j], ln);
-            else if (ln == 2) idct4(t);
-            else if (ln == 3) idct8(t);
-            else idct16(t);
-#pragma unroll
-            for (int j = 0; j < 16; j++)
-                if (j < sz) {
-                    const int32_t v = rs ? (t[j] + (1 << (rs - 1))) >> rs : t[j];
-                    L.b[o + i * sz + j] = sk_clip(v, -32768, 32767);
-                }
+            inv_rows_lane(L, p ? log2n - 1 : log2n, base(p), i, idtx && p < np);
         }
     }
     wsync();
     {
         const int p = l < rows_y ? 0 : (l < rows_y + rows_c ? 1 : (l < rows_y + 2 * rows_c ? 2 : 3));
         if (p < 3) {
-            const int ln = p ? log2n - 1 : log2n, sz = 1 << ln, o = base(p);
             const int j = p == 0 ? l : (p == 1 ? l - rows_y : l - rows_y - rows_c);
-            int32_t t[16];
-#pragma unroll
-            for (int i = 0; i < 16; i++) t[i] = i < sz ? L.b[o + i * sz + j] : 0;
-            if (idtx && p < np)
-#pragma unroll
-                for (int i = 0; i < 16; i++) t[i] = iidentity(t[i], ln);
-            else if (ln == 2) idct4(t);
-            else if (ln == 3) idct8(t);
-            else idct16(t);
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-                if (i < sz) {
-                    const int k = o + i * sz + j;
-                    L.pred[k] = (uint8_t)sk_clip255((int)L.pred[k] + ((t[i] + 8) >> 4));
-                }
+            inv_cols_lane(L, p ? log2n - 1 : log2n, base(p), j, idtx && p < np);
         }
     }
     wsync();
     return cul | (nzm ? (1u << 24) : 0u) | (idtx && nzm ? (1u << 25) : 0u);   // no levels: DCT_DCT
+}
+
+// av1_cfl: both chroma planes of an intra block coded again, DCT_DCT, from the prediction in
+// L.pred (code_block_wave's forward steps on planes 1 and 2): levels into L.lv, returns the J of
+// both planes (av1_cpu.cpp quant_block). recon_chroma_wave then reconstructs them into L.pred and
+// returns their level summaries in bytes 1 and 2.
+__device__ long long recode_chroma_wave(BlkLds& L, const FdctLds& F, int log2n, int qidx) {
+    const int l = lane(), ln = log2n - 1, cnn = 1 << (2 * ln);
+    const int qd = dc_q(qidx), qa = ac_q(qidx);
+    for (int o = 256; o <= 320; o += 64)
+        for (int i = l; i < cnn; i += 64) L.a[o + i] = (int)L.src[o + i] - (int)L.pred[o + i];
+    wsync();
+    for (int o = 256; o <= 320; o += 64) fwd_cols_plane(L, F, ln, o);
+    wsync();
+    long long j = 0;
+    for (int o = 256; o <= 320; o += 64) {
+        long long ed = 0, ei = 0;
+        fwd_rows_quant_plane(L, F, ln, o, qd, qa, true, false, ed, ei);
+        const long long dp = wsum64(ed);
+        wsync();
+        j += tx_rd_cost(4 * dp, rate2_wave(L.lv + o, ln), qa);
+    }
+    return j;
+}
+__device__ uint32_t recon_chroma_wave(BlkLds& L, int log2n, int qidx) {
+    const int l = lane(), ln = log2n - 1, cn = 1 << ln;
+    const int qd = dc_q(qidx), qa = ac_q(qidx);
+    uint32_t cul = 0;
+    for (int p = 1; p < 3; p++) cul |= dequant_plane<false>(L, ln, p == 1 ? 256 : 320, qd, qa, nullptr) << (8 * p);
+    wsync();
+    const int o = l < cn ? 256 : 320, k = l < cn ? l : l - cn;   // lane = row, then column, of one plane
+    if (l < 2 * cn) inv_rows_lane(L, ln, o, k, false);
+    wsync();
+    if (l < 2 * cn) inv_cols_lane(L, ln, o, k, false);
+    wsync();
+    return cul;
 }
 
 // Block loads / stores (luma n at (x, y); chroma n/2 at (x/2, y/2)).
@@ -679,7 +737,8 @@ __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
 // the block is worked out in LDS and becomes the block's coding - reconstruction, levels, level
 // contexts, cells - only where its J plus the mode-bits bias is below the inter coding's
 // (av1_cpu.cpp intra_trial); otherwise nothing is stored.
-template <bool kTrial, bool kUv>
+// kTools: the session's chroma tools, bit 0 av1_chroma_palette (kUv), bit 1 av1_cfl (kCfl).
+template <bool kTrial, int kTools>
 __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, int r, int c, int bsl, int qidx, int cand) {
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
@@ -688,6 +747,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     const TileRect t = tile_of(g, r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
     const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
+    constexpr bool kUv = (kTools & 1) != 0, kCfl = (kTools & 2) != 0;
     BlkInfo b{};
     if (kTrial) {
         b.bsl = (uint8_t)bsl;
@@ -713,12 +773,13 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         L.pred[320 + i] = (uint8_t)dcv;
     }
     wsync();
-    // levels in LDS until the decisions are made: a trial, or a session with chroma palettes
-    // (kUv), whose decision needs the chroma J; otherwise code_block_wave stores them
-    constexpr bool in_lds = kTrial || kUv;
+    // levels in LDS until the decisions are made: a trial, or a session with chroma palettes or
+    // CfL (kTools), whose decisions need the chroma J; otherwise code_block_wave stores them
+    constexpr bool in_lds = kTrial || kTools != 0;
     uint32_t s = code_block_wave<in_lds ? 2 : 0>(L, F, log2n, qidx, true, lev_ptr(A, r, c, bsl, 0),
                                                  lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
     long long jreg = L.jreg;
+    const uint32_t sdc = s;   // the UV_DC_PRED coding's summaries (the CfL gate)
     b.tx_type = (int16_t)((s >> 25) & 1 ? TX_IDTX : TX_DCT_DCT);
     // palette candidate from k_av1_intra_modes (colours already in the palette cells):
     // exact palette of the source luma vs the transform path (av1_cpu.cpp intra_block)
@@ -742,7 +803,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     }
     // chroma palette candidate (av1_chroma_palette): the exact pairs of the source chroma vs both
     // DCT planes (av1_cpu.cpp intra_code)
-    long long jchr = kTrial ? L.jchr : 0;
+    long long jchr = kTrial || kCfl ? L.jchr : 0;
     if (kUv && kuv && tx_rd_cost(0, A.pal_rate_uv[cell], ac_q(qidx)) < L.jchr) {   // kuv: levels in LDS
         jchr = tx_rd_cost(0, A.pal_rate_uv[cell], ac_q(qidx));
         b.pal_n = (uint8_t)(b.pal_n | (kuv << 4));
@@ -754,6 +815,70 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         s &= ~0xffff00u;   // no chroma levels: the summary and the skip flag come from luma
         s = (s & ~(1u << 24)) | ((s & 0xffu) ? (1u << 24) : 0u);
         wsync();
+    }
+    // chroma from luma (av1_cfl; av1_cpu.cpp intra_code): a block whose UV_DC_PRED coding kept a
+    // chroma level and whose subsampled luma reconstruction varies. One chroma sample per lane
+    // (64 or 16 lanes); sums by wave reductions, every decision wave-uniform. The coding standing
+    // (levels, reconstruction) waits in the chroma half of L.lv2 and in L.a's luma part, both dead
+    // after code_block_wave, while both planes are coded again from the CfL prediction.
+    if (kCfl && (sdc & 0xffff00u)) {
+        const int cl2 = log2n - 1, cnn = cn * cn;
+        const bool act = l < cnn;
+        const int lum = act ? cfl_luma(L.pred, n, l >> cl2, l & (cn - 1)) : 0;
+        const int avg = cfl_avg(wsum(lum), cl2);   // every lane takes part in the sum
+        const int ac = act ? lum - avg : 0;
+        if (__ballot(ac != 0)) {
+            const long long sxx = wsum(ac * ac);   // <= 64 x 2040^2 < 2^31
+            const int dcu = intra_dc(E[1], cl2), dcv = intra_dc(E[2], cl2);
+            const int su = act ? L.src[256 + l] : 0, sv = act ? L.src[320 + l] : 0;
+            int au = 0, av = 0;
+            for (int p = 0; p < 2; p++) {
+                const int dc = p ? dcv : dcu, sp = p ? sv : su;
+                const long long sxy = wsum(act ? ac * (sp - dc) : 0);
+                const int a0 = cfl_alpha0(sxx, sxy);
+                int best = 0x7fffffff, alpha = 0;
+                for (int q = 0; q < 3; q++) {
+                    const int a = cfl_cand(a0, sxy, q);
+                    const int e = act ? sp - cfl_px(dc, a, ac) : 0;
+                    const int sse = wsum(e * e);
+                    if (sse < best) {
+                        best = sse;
+                        alpha = a;
+                    }
+                }
+                if (p) av = alpha;
+                else au = alpha;
+            }
+            if (au || av) {
+                if (act) {
+                    L.lv2[256 + l] = L.lv[256 + l];
+                    L.lv2[320 + l] = L.lv[320 + l];
+                    L.a[l] = L.pred[256 + l];
+                    L.a[64 + l] = L.pred[320 + l];
+                    L.pred[256 + l] = (uint8_t)cfl_px(dcu, au, ac);
+                    L.pred[320 + l] = (uint8_t)cfl_px(dcv, av, ac);
+                }
+                wsync();
+                const long long jcfl = recode_chroma_wave(L, F, log2n, qidx) + tx_rd_cost(0, cfl_rate2(au, av), ac_q(qidx));
+                if (jcfl < jchr) {
+                    jchr = jcfl;
+                    b.uv_mode = UV_CFL_PRED;
+                    b.pal_n &= 15;
+                    b.mv_row = (int16_t)au;
+                    b.mv_col = (int16_t)av;
+                    s = (s & ~0xffff00u) | recon_chroma_wave(L, log2n, qidx);
+                    s = (s & ~(1u << 24)) | ((s & 0xffffffu) ? (1u << 24) : 0u);
+                } else {
+                    if (act) {
+                        L.lv[256 + l] = L.lv2[256 + l];
+                        L.lv[320 + l] = L.lv2[320 + l];
+                        L.pred[256 + l] = (uint8_t)L.a[l];
+                        L.pred[320 + l] = (uint8_t)L.a[64 + l];
+                    }
+                    wsync();
+                }
+            }
+        }
     }
     if (kTrial) {
         // wave-uniform: every lane reads the same words
@@ -777,7 +902,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
 }
 
 // Key frames: one workgroup (16 waves) per tile; unit (x, y) of the tile at step x + y.
-template <bool kUv>
+template <int kTools>
 __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[16];
@@ -803,7 +928,7 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
             for (int k = 0; k < nb; k++) {
                 int r, c;
                 unit_block(g, uy0 + y, ux0 + x, k, r, c);
-                intra_rec_block<false, kUv>(A, Lw[w], F, r, c, bsl, qidx, -1);
+                intra_rec_block<false, kTools>(A, Lw[w], F, r, c, bsl, qidx, -1);
             }
         }
         __syncthreads();
@@ -816,7 +941,7 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
 // as it stands (an inter neighbour's is final, a candidate neighbour's was decided at an earlier
 // step). A tile without candidates returns before loading anything; a unit without one costs
 // its wave nothing but the step's barrier.
-template <bool kUv>
+template <int kTools>
 __global__ __launch_bounds__(1024) void k_av1_inter_intra(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[16];
@@ -846,7 +971,7 @@ __global__ __launch_bounds__(1024) void k_av1_inter_intra(Av1Args A) {
                 int r, c;
                 unit_block(g, uy0 + y, ux0 + x, k, r, c);
                 const int cand = A.cand[(size_t)(r >> 1) * g.c8 + (c >> 1)];
-                if (cand & 1) intra_rec_block<true, kUv>(A, Lw[w], F, r, c, bsl, qidx, cand);
+                if (cand & 1) intra_rec_block<true, kTools>(A, Lw[w], F, r, c, bsl, qidx, cand);
             }
         }
         __syncthreads();
@@ -1301,8 +1426,9 @@ __device__ __forceinline__ void code_palette_tokens_uv(WaveTokenSink& w, const C
     wsync();
 }
 
-// kUv: the session runs with av1_chroma_palette (code_unit's chroma palette syntax compiled in).
-template <bool kUv>
+// kTools: bit 0, the session runs with av1_chroma_palette (code_unit's chroma palette syntax compiled
+// in); bit 1, with av1_cfl (the CfL alphas' syntax).
+template <int kTools>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_av1_tokens(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ uint32_t bits_w[4][256];
@@ -1335,7 +1461,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     const int ux = u % f.mb_w, uy = u / f.mb_w;
     WaveTokenSink sink{A.tok + (size_t)u * kTokCap, 0, kTokCap, 0u, 0, bits_w[w]};
     const TileRect t = tile_of(g, uy * 4, ux * 4);
-    code_unit<WaveTokenSink, kUv>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
+    code_unit<WaveTokenSink, (kTools & 1) != 0, (kTools & 2) != 0>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
     sink.flush();
     if (lane() == 0) A.tok_n[u] = sink.n;
 }
@@ -2007,33 +2133,48 @@ void ec_buffers(int tiles, int tile_bytes, int* max_blocks, int* vcap) {
     *vcap = tile_bytes / 4 + 8;
 }
 
+// The kernels that depend on the session's chroma tools (kTools: bit 0 av1_chroma_palette, bit 1
+// av1_cfl): the ones with the candidate, decision and syntax in place of the ones without, the
+// same launches either way. The open-loop mode kernels know the chroma palette only.
+template <int kTools>
+static void launch_intra(const Av1Args& a, int n, int tiles, hipStream_t s) {
+    hipLaunchKernelGGL(k_av1_intra_modes<(kTools & 1) != 0>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_av1_intra_rec<kTools>, dim3(tiles), dim3(1024), 0, s, a);
+}
+template <int kTools>
+static void launch_inter_intra(const Av1Args& a, int n, int tiles, hipStream_t s) {
+    hipLaunchKernelGGL(k_av1_cand_modes<(kTools & 1) != 0>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_av1_inter_intra<kTools>, dim3(tiles), dim3(1024), 0, s, a);
+}
+template <int kTools>
+static void launch_tokens(const Av1Args& a, int n, hipStream_t s) {
+    hipLaunchKernelGGL(k_av1_tokens<kTools>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+}
+#define SK_BY_TOOLS(tools, call)            \
+    switch (tools) {                        \
+        case 0: call(0); break;             \
+        case 1: call(1); break;             \
+        case 2: call(2); break;             \
+        default: call(3); break;            \
+    }
+
 // Block decisions, reconstruction and the arithmetic-coded tiles: everything the coded
 // size depends on (the K10 guard re-runs it, gated).
 static void launch_code(const Av1Args& a, hipStream_t s) {
     const int n = a.f.mb_w * a.f.mb_h;
     const int tiles = a.geo.tile_cols * a.geo.tile_rows;
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
-    // av1_chroma_palette: the kernels with the chroma candidate, decision and syntax in place of
-    // the ones without (the same launches either way)
-    const bool uv = a.chroma_palette != 0;
-    if (uv) {
-        hipLaunchKernelGGL(k_av1_intra_modes<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_av1_intra_rec<true>, dim3(tiles), dim3(1024), 0, s, a);
-    } else {
-        hipLaunchKernelGGL(k_av1_intra_modes<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_av1_intra_rec<false>, dim3(tiles), dim3(1024), 0, s, a);
-    }
+    const int tools = (a.chroma_palette ? 1 : 0) | (a.cfl ? 2 : 0);
+#define SK_INTRA(k) launch_intra<k>(a, n, tiles, s)
+    SK_BY_TOOLS(tools, SK_INTRA)
+#undef SK_INTRA
     const bool ltr_on = a.f.ltr_cfg.mode == ltr::LTR_BUFMAP;
     if (a.intra_inter) {   // av1_intra_inter: the inter coding with its J, then the candidates as intra blocks
         if (ltr_on) hipLaunchKernelGGL((k_av1_inter<true, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_av1_inter<false, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
-        if (uv) {
-            hipLaunchKernelGGL(k_av1_cand_modes<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_av1_inter_intra<true>, dim3(tiles), dim3(1024), 0, s, a);
-        } else {
-            hipLaunchKernelGGL(k_av1_cand_modes<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_av1_inter_intra<false>, dim3(tiles), dim3(1024), 0, s, a);
-        }
+#define SK_INTER_INTRA(k) launch_inter_intra<k>(a, n, tiles, s)
+        SK_BY_TOOLS(tools, SK_INTER_INTRA)
+#undef SK_INTER_INTRA
     } else if (ltr_on) {
         hipLaunchKernelGGL((k_av1_inter<true, false>), dim3((n + 3) / 4), dim3(256), 0, s, a);
     } else {
@@ -2041,8 +2182,9 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     }
     hipLaunchKernelGGL(k_av1_merge, dim3(a.geo.sb_cols * a.geo.sb_rows), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_av1_modes, dim3((a.geo.c8 * a.geo.r8 + 255) / 256), dim3(256), 0, s, a);
-    if (uv) hipLaunchKernelGGL(k_av1_tokens<true>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_av1_tokens<false>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+#define SK_TOKENS(k) launch_tokens<k>(a, n, s)
+    SK_BY_TOOLS(tools, SK_TOKENS)
+#undef SK_TOKENS
     hipLaunchKernelGGL(k_av1_tok_scan, dim3(tiles), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_tok_copy, dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_cdf, dim3(tiles * kEcParts), dim3(64), 0, s, a);

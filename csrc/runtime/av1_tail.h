@@ -38,6 +38,7 @@ struct Av1Tail {
         a.chroma_palette = cfg.av1_chroma_palette > 0 && a.palette;
         a.pal_uv = mem.dmalloc<uint8_t>((size_t)geo_.c8 * geo_.r8 * 16);
         a.pal_rate_uv = mem.dmalloc<int>((size_t)geo_.c8 * geo_.r8);
+        a.cfl = cfg.av1_cfl > 0;
         a.intra_inter = cfg.av1_intra_inter > 0;
         if (a.intra_inter) {   // av1_gpu.h: the inter coding's J, the intra candidates and their count per tile
             a.jinter = mem.dmalloc<long long>((size_t)geo_.c8 * geo_.r8);

@@ -45,7 +45,8 @@ int sk_av1_cdf_field(int i, int32_t* off, int32_t* nsym, int32_t* count, int32_t
                     SK_FIELD(partition_w8, 4, 11),  SK_FIELD(eob_pt_16, 5, 6),             SK_FIELD(eob_pt_1024, 11, 12),
                     SK_FIELD(coeff_base, 4, 5),     SK_FIELD(coeff_br, 4, 5),              SK_FIELD(coeff_base_eob, 3, 4),
                     SK_FIELD(txb_skip, 2, 3),       SK_FIELD(skip, 2, 3),                  SK_FIELD(mv_joint, 4, 5),
-                    SK_FIELD(palette_uv_size, 7, 8)};   // palette_uv_color's rows have 2..8 symbols: no one N to list
+                    SK_FIELD(palette_uv_size, 7, 8),   // palette_uv_color's rows have 2..8 symbols: no one N to list
+                    SK_FIELD(cfl_sign, 8, 9),       SK_FIELD(cfl_alpha, 16, 17)};
 #undef SK_FIELD
     const int nf = (int)(sizeof(fs) / sizeof(fs[0]));
     if (i < 0 || i >= nf) return nf;

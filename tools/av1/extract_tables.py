@@ -206,6 +206,21 @@ def main():
     put("palette_uv_size", img.aom_table([8713, 19979, 27128, 29609, 31331, 32272], 7, 8, 7), [7], 8)
     put("palette_uv_color", img.aom_table([[29089], [16384], [8713], [29257], [31610]], 35, 9,
                                           [n for n in range(2, 9) for _ in range(5)]), [7, 5], 9)
+    # chroma from luma (av1_cfl): the joint sign CDF (8 symbols) and the magnitude CDFs [6 contexts] (16 symbols)
+    # cfl_sign is a single row of dav1d's struct (8 words: seven values and the counter); the signature also
+    # occurs in unrelated data, so take the first hit that is a CDF row
+    sign = None
+    for hit in img.find([32768 - v for v in [1418, 2123, 13340]]):
+        raw = img.u16[hit // 2: hit // 2 + 8].tolist()
+        vals = [32768 - x for x in raw[:7]] + [32768]
+        if hit % 2 == 0 and raw[7] == 0 and all(y > x for x, y in zip(vals, vals[1:])):
+            sign = vals
+            break
+    if sign is None:
+        raise SystemExit("cfl_sign cdf not found")
+    check(sign, 8, "cfl_sign")
+    put("cfl_sign", [sign], [], 9)
+    put("cfl_alpha", img.aom_table([7637, 20719, 31401], 6, 17, 16), [6], 17)
     # ---- motion vectors (libaom nmv_context: joints, then two nmv_component structs)
     mv = img.aom_struct([4096, 11264, 19328], [(1, 4), (1, 11), (2, 4), (1, 4), (1, 2), (1, 2), (1, 2), (1, 2), (10, 2),
                                                (1, 11), (2, 4), (1, 4), (1, 2), (1, 2), (1, 2), (1, 2), (10, 2)])
@@ -274,7 +289,7 @@ def main():
     w("namespace sk::av1 {")
     w("")
     # tables added after the first layout go behind the coefficient part: every earlier CDF keeps its offset
-    tail_names = ["palette_uv_size", "palette_uv_color"]
+    tail_names = ["palette_uv_size", "palette_uv_color", "cfl_sign", "cfl_alpha"]
     mode_names = [k for k in T if k not in ("txb_skip", "eob_extra", "dc_sign", "coeff_base_eob", "coeff_base",
                                             "coeff_br") and not k.startswith("eob_pt") and k not in tail_names]
     coef_names = ["txb_skip", "eob_extra", "dc_sign", "eob_pt_16", "eob_pt_32", "eob_pt_64", "eob_pt_128",
