@@ -1429,15 +1429,20 @@ SK_HD void code_palette_mode_info(Sink& w, const CdfContext& cx, const FrameView
 }
 
 // palette_tokens: the colour index map, first index as ns(k), then every other sample on
-// anti-diagonals (top-right to bottom-left) as its rank in the neighbour colour order.
-template <class Sink>
-SK_HD void code_palette_tokens(Sink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl, int k) {
+// anti-diagonals (top-right to bottom-left) as its rank in the neighbour colour order. kNear: the
+// session's map is the nearest colour (av1_palette_cluster, palette_map_index below).
+template <bool B>
+struct BoolTag {};
+template <bool kNear>
+SK_HD int palette_map_index(const uint8_t* col, int k, int v);
+template <class Sink, bool kNear>
+SK_HD void code_palette_tokens(Sink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl, int k, BoolTag<kNear>) {
     const int n = 4 << bsl;
     const uint8_t* col = v.pal_at(r, c);
     uint8_t map[256];
     for (int i = 0; i < n; i++)
         for (int j = 0; j < n; j++)
-            map[i * n + j] = (uint8_t)palette_index(col, k, v.src_y[(size_t)(r * 4 + i) * v.stride_y + c * 4 + j]);
+            map[i * n + j] = (uint8_t)palette_map_index<kNear>(col, k, v.src_y[(size_t)(r * 4 + i) * v.stride_y + c * 4 + j]);
     code_ns(w, k, map[0]);
     for (int d = 1; d < 2 * n - 1; d++)
         for (int j = sk_min(d, n - 1); j >= sk_max(0, d - n + 1); j--) {
@@ -1499,6 +1504,111 @@ SK_HD int palette_rate2_px(const uint8_t* map, int n, int i, int j, int k) {
     if (i == 0 && j == 0) return 2 * ceil_log2(k);
     const bool rep = (j > 0 && map[i * n + j - 1] == x) || (i > 0 && map[(i - 1) * n + j] == x);
     return rep ? 1 : 2 + 2 * ceil_log2(k);
+}
+
+// ---------------------------------------------------------------------------------
+// Clustered luma palettes (av1_palette_cluster): a fully visible intra block whose source luma holds
+// more than kPalMax distinct values (anti-aliased text) coded as a palette of 2..8 colours that need
+// not be source values, each sample on its nearest colour, plus a DCT_DCT / IDTX luma residual against
+// that prediction. The bitstream allows all of it: palette blocks carry a residual like any DC_PRED
+// block, and the index map is the encoder's choice. Encoder choice (docs/design.md), integers only,
+// from the block's 256-bin histogram, so that the CPU loop (palette_cluster) and the wave-parallel
+// one of the kernels (intra_mode_wave) agree bit for bit:
+//   candidates  kPalMax < m <= kPalClusterValues distinct values, and tol = ac_q / 12 >= 1. tol is the
+//               largest sample error that IDTX quantises to nothing (quantize: 8 |e| < 2 q / 3).
+//               No ramp: more than kPalMax values in a row, each at most kPalClusterRampGap above the
+//               one before, are a gradient and not a set of colours (palette_has_ramp).
+//   count       k = the fewest intervals of width 2 tol that hold every value (greedily from the
+//               lowest value), at most kPalMax. One interval: no palette.
+//   colours     the m values start as m groups in ascending order; the adjacent pair with the least
+//               palette_merge_cost (ties to the lower pair) merges until k groups are left: a fixed
+//               m - k steps. A colour is the rounded mean of its group (palette_cluster_mean).
+// The colours are strictly ascending: the groups are disjoint ranges of values in ascending order,
+// and a rounded mean lies within its group's range.
+constexpr int kPalClusterValues = 32;
+constexpr int kPalClusterRampGap = 2;
+constexpr int kPalClusterMark = 1 << 30;   // kernels: bit of a pal_rate word that marks a clustered candidate
+SK_HD int palette_cluster_tol(int qidx) { return ac_q(qidx) / 12; }
+SK_HD int palette_cluster_mean(int sum, int cnt) { return (2 * sum + cnt) / (2 * cnt); }   // cnt > 0; halves go up
+// What merging two groups (sum of samples, sample count) adds to the squared error, from their rounded
+// means: n1 n2 d^2 / (n1 + n2). A block has at most 256 samples, so n1 n2 <= 2^14 and the product
+// stays below 2^31; the cost is below 2^23.
+SK_HD int palette_merge_cost(int s1, int n1, int s2, int n2) {
+    const int d = palette_cluster_mean(s2, n2) - palette_cluster_mean(s1, n1);
+    return (n1 * n2 * d * d) / (n1 + n2);
+}
+// links: bit i set where the value of rank i + 1 is at most kPalClusterRampGap above the value of rank i.
+// kPalMax links in a row are kPalMax + 1 values in a row.
+SK_HD bool palette_has_ramp(uint64_t links) {
+    links &= links >> 1;
+    links &= links >> 2;
+    links &= links >> 4;
+    return links != 0;
+}
+// Index of the colour (packed, pal_byte) nearest to v, ties to the lower index.
+SK_HD int palette_nearest(uint64_t C, int k, int v) {
+    int x = 0, best = 256;
+    for (int q = 0; q < k; q++) {
+        const int d = sk_abs((int)((C >> (8 * q)) & 255u) - v);
+        if (d < best) {
+            best = d;
+            x = q;
+        }
+    }
+    return x;
+}
+// The index map of a palette block of the session: kNear (av1_palette_cluster) the nearest colour,
+// which for an exact palette is the colour itself; else palette_index as it was.
+template <bool kNear>
+SK_HD int palette_map_index(const uint8_t* col, int k, int v) {
+    if (!kNear) return palette_index(col, k, v);
+    uint64_t C = 0;
+    for (int q = 0; q < kPalMax; q++) C |= (uint64_t)col[q] << (8 * q);
+    return palette_nearest(C, k, v);
+}
+// Host side (the kernels work per wave): the colours of the block whose luma histogram is hist, when it
+// is a candidate (returns their count and col strictly ascending, zero-filled to kPalMax; else 0).
+inline int palette_cluster(const uint16_t* hist, int tol, uint8_t* col) {
+    int m = 0, s[kPalClusterValues], n[kPalClusterValues];
+    for (int v = 0; v < 256; v++) {
+        if (!hist[v]) continue;
+        if (m == kPalClusterValues) return 0;
+        s[m] = v * hist[v];
+        n[m++] = hist[v];
+    }
+    if (m <= kPalMax || tol < 1) return 0;
+    uint64_t links = 0;
+    for (int i = 0; i + 1 < m; i++)
+        if (s[i + 1] / n[i + 1] - s[i] / n[i] <= kPalClusterRampGap) links |= 1ull << i;
+    if (palette_has_ramp(links)) return 0;
+    int k = 0;
+    for (int i = 0, hi = -1; i < m; i++) {
+        const int v = s[i] / n[i];
+        if (v > hi) {
+            k++;
+            hi = v + 2 * tol;
+        }
+    }
+    if (k < 2) return 0;
+    if (k > kPalMax) k = kPalMax;
+    for (; m > k; m--) {
+        int best = 0x7fffffff, bi = 0;
+        for (int i = 0; i + 1 < m; i++) {
+            const int cost = palette_merge_cost(s[i], n[i], s[i + 1], n[i + 1]);
+            if (cost < best) {
+                best = cost;
+                bi = i;
+            }
+        }
+        s[bi] += s[bi + 1];
+        n[bi] += n[bi + 1];
+        for (int i = bi + 1; i + 1 < m; i++) {
+            s[i] = s[i + 1];
+            n[i] = n[i + 1];
+        }
+    }
+    for (int q = 0; q < kPalMax; q++) col[q] = q < k ? (uint8_t)palette_cluster_mean(s[q], n[q]) : 0;
+    return k;
 }
 
 // ---------------------------------------------------------------------------------
@@ -1567,7 +1677,9 @@ struct DecodedBefore {
 
 // Mode info + residual of one block (§5.11.5 decode_block). kCfl = false compiles the CfL alphas'
 // syntax out, as kUv does the chroma palette's: the GPU token kernel of sessions without av1_cfl.
-template <class Sink, bool kUv = true, bool kCfl = true>
+// kNear = false: luma index maps by palette_index, the token kernel of sessions without av1_palette_cluster
+// (the nearest colour of an exact palette is the same index).
+template <class Sink, bool kUv = true, bool kCfl = true, bool kNear = true>
 SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int r, int c, int bsl) {
     const BlkInfo& b = v.at(r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
@@ -1636,7 +1748,7 @@ SK_HD void code_block(Sink& w, const CdfContext& cx, const FrameView& v, const T
             code_mv(w, cx, b.mv_row - s.mv[pos][0], b.mv_col - s.mv[pos][1]);
         }
     }
-    if (pal_ny(b)) code_palette_tokens(w, cx, v, r, c, bsl, pal_ny(b));
+    if (pal_ny(b)) code_palette_tokens(w, cx, v, r, c, bsl, pal_ny(b), BoolTag<kNear>{});
     if (kUv && pal_nuv(b)) code_palette_tokens_uv(w, cx, v, r, c, bsl, pal_nuv(b));
     if (blk_skip(b)) return;
     code_coeffs(w, cx, v.levels(r, c, bsl, 0), bsl, 0, coef_ctx(v, t, 0, c, r, 1 << bsl), blk_inter(b), b.mode, v.qidx,
@@ -1670,7 +1782,7 @@ SK_HD bool code_partition_symbol(Sink& w, const CdfContext& cx, const FrameView&
 // partition symbols of the 64 / 32 nodes it opens, then its own block(s); a unit
 // inside a larger (merged) block contributes nothing. Units in Z order within
 // raster superblocks reproduce decode_partition's order exactly.
-template <class Sink, bool kUv = true, bool kCfl = true>
+template <class Sink, bool kUv = true, bool kCfl = true, bool kNear = true>
 SK_HD void code_unit(Sink& w, const CdfContext& cx, const FrameView& v, const TileRect& t, int ux, int uy) {
     const int r = uy * 4, c = ux * 4;
     if (r >= v.geo.mi_rows || c >= v.geo.mi_cols) return;
@@ -1682,19 +1794,19 @@ SK_HD void code_unit(Sink& w, const CdfContext& cx, const FrameView& v, const Ti
             continue;
         }
         if (code_partition_symbol(w, cx, v, t, r, c, L)) {
-            code_block<Sink, kUv, kCfl>(w, cx, v, t, r, c, L);
+            code_block<Sink, kUv, kCfl, kNear>(w, cx, v, t, r, c, L);
             return;
         }
     }
     if (code_partition_symbol(w, cx, v, t, r, c, 2)) {
-        code_block<Sink, kUv, kCfl>(w, cx, v, t, r, c, 2);
+        code_block<Sink, kUv, kCfl, kNear>(w, cx, v, t, r, c, 2);
         return;
     }
     for (int q = 0; q < 4; q++) {
         const int rr = r + (q >> 1) * 2, cc = c + (q & 1) * 2;
         if (rr >= v.geo.mi_rows || cc >= v.geo.mi_cols) continue;
         code_partition_symbol(w, cx, v, t, rr, cc, 1);
-        code_block<Sink, kUv, kCfl>(w, cx, v, t, rr, cc, 1);
+        code_block<Sink, kUv, kCfl, kNear>(w, cx, v, t, rr, cc, 1);
     }
 }
 

@@ -205,6 +205,7 @@ CpuAv1Encoder::CpuAv1Encoder(const h264::EncoderConfig& cfg, int tcl, int trl) :
     pal_uv.assign((size_t)geo.c8 * geo.r8 * 16, 0);
     chroma_palette = cfg.av1_chroma_palette > 0;
     cfl = cfg.av1_cfl > 0;
+    palette_cluster = cfg.av1_palette_cluster > 0;
     jinter.assign((size_t)geo.c8 * geo.r8, 0);
     intra_inter = cfg.av1_intra_inter > 0;
     lctx_h[1] = lctx_h[2] = geo.mi_rows >> 1;
@@ -391,6 +392,37 @@ void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mod
             b.tx_type = TX_DCT_DCT;
             memset(ly, 0, sizeof(int16_t) * n * n);
             for (int i = 0; i < n; i++) memcpy(&py[i * n], sy + (size_t)i * g.stride_y, (size_t)n);
+        }
+    }
+    // clustered palette (av1_palette_cluster, av1_core.h): a block with more than kPalMax values that the
+    // open-loop rule admits; the palette prediction codes luma once more, DCT_DCT or IDTX, against the J standing
+    if (palette_cluster && fp.screen && visible && !k) {
+        uint16_t hist[256] = {0};
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) hist[sy[(size_t)i * g.stride_y + j]]++;
+        const int kc = sk::av1::palette_cluster(hist, palette_cluster_tol(fp.qidx), col);
+        if (kc) {
+            uint8_t map[256], pp[256];
+            int16_t ld[256];
+            int rate2 = palette_rate2_head(kc);
+            for (int i = 0; i < n; i++)
+                for (int j = 0; j < n; j++) {
+                    map[i * n + j] = (uint8_t)palette_map_index<true>(col, kc, sy[(size_t)i * g.stride_y + j]);
+                    pp[i * n + j] = col[map[i * n + j]];
+                }
+            for (int i = 0; i < n; i++)
+                for (int j = 0; j < n; j++) rate2 += palette_rate2_px(map, n, i, j, kc);
+            const long long jd2 = quant_block(sy, g.stride_y, pp, log2n, fp.qidx, true, TX_DCT_DCT, ld);
+            const long long ji2 = quant_block(sy, g.stride_y, pp, log2n, fp.qidx, true, TX_IDTX, lid);
+            const long long jp = (jd2 < ji2 ? jd2 : ji2) + tx_rd_cost(0, rate2, ac_q(fp.qidx));
+            if (jp < o.jy) {
+                o.jy = jp;
+                b.pal_n = (uint8_t)kc;
+                b.mode = DC_PRED;
+                b.tx_type = (int16_t)(ji2 < jd2 && any_nonzero(lid, n * n) ? TX_IDTX : TX_DCT_DCT);
+                memcpy(ly, b.tx_type == TX_IDTX ? lid : ld, sizeof(int16_t) * n * n);
+                memcpy(py, pp, (size_t)n * n);
+            }
         }
     }
     bool nz = recon_block(ly, log2n, fp.qidx, true, b.tx_type, py, o.rec, n);

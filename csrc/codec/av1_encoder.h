@@ -122,6 +122,7 @@ class CpuAv1Encoder {
     bool intra_inter = false;        // EncoderConfig::av1_intra_inter
     bool chroma_palette = false;     // EncoderConfig::av1_chroma_palette (acts where palettes do: fp.screen)
     bool cfl = false;                // EncoderConfig::av1_cfl (acts on every intra block)
+    bool palette_cluster = false;    // EncoderConfig::av1_palette_cluster (acts where palettes do: fp.screen)
     std::vector<long long> jinter;   // c8 * r8: J of the inter coding of the block at that origin cell (inter_block)
     int lctx_w[3] = {0, 0, 0}, lctx_h[3] = {0, 0, 0};
     int level_idx = 8;

@@ -69,6 +69,9 @@ struct EncoderConfig {
     int av1_cfl = 0;             // AV1: chroma from luma (UV_CFL_PRED) on intra blocks, where it costs less by RD than the
                                  // chroma coding standing (key frames; inter frames with av1_intra_inter); the other
                                  // codecs ignore it
+    int av1_palette_cluster = 0; // AV1: luma palettes of clustered colours with a residual on intra blocks whose source
+                                 // luma holds more than 8 values (anti-aliased text), where luma palettes may occur; the
+                                 // other codecs ignore it
 };
 
 // Long-term cache slots in force (the three codecs share this configuration and the front end).

@@ -79,6 +79,8 @@ struct Av1Args {
                               // bits 20..23 of cand (inter frames)
     int cfl;                  // EncoderConfig::av1_cfl: chroma from luma on intra blocks (k_av1_intra_rec, k_av1_inter_intra,
                               // k_av1_tokens; the alphas ride in an intra cell's mv_row / mv_col, av1_core.h)
+    int palette_cluster;      // EncoderConfig::av1_palette_cluster (and palette): clustered luma palettes with a residual.
+                              // A clustered candidate is marked by bit 30 of its pal_rate word (kPalClusterMark)
     int intra_inter;          // EncoderConfig::av1_intra_inter: intra blocks in inter frames; the three below only then
     long long* jinter;        // [r8][c8] J of the inter coding of the block at that origin cell (k_av1_inter)
     int* cand;                // [r8][c8] bit 0: the block is an intra candidate (its inter coding kept levels),

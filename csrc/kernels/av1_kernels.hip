@@ -398,6 +398,42 @@ __device__ long long recode_chroma_wave(BlkLds& L, const FdctLds& F, int log2n, 
     }
     return j;
 }
+// av1_palette_cluster: the luma of an intra block coded again from the prediction in L.pred
+// (code_block_wave's forward steps on plane 0, both transform types): DCT levels into L.lv, IDTX levels
+// into L.lv2, returns the J of the cheaper type (av1_cpu.cpp quant_block) and in *idtx whether IDTX is
+// the cheaper one and keeps a level. recon_luma_wave then makes the chosen levels L.lv, reconstructs
+// into L.pred and returns the luma level summary.
+__device__ long long recode_luma_wave(BlkLds& L, const FdctLds& F, int log2n, int qidx, bool* idtx) {
+    const int l = lane(), nn = 1 << (2 * log2n);
+    const int qd = dc_q(qidx), qa = ac_q(qidx);
+    for (int i = l; i < nn; i += 64) L.a[i] = (int)L.src[i] - (int)L.pred[i];
+    wsync();
+    fwd_cols_plane(L, F, log2n, 0);
+    wsync();
+    long long ed = 0, ei = 0;
+    fwd_rows_quant_plane(L, F, log2n, 0, qd, qa, true, true, ed, ei);
+    const long long dp = wsum64(ed), ip = wsum64(ei);
+    wsync();
+    const long long jd = tx_rd_cost(4 * dp, rate2_wave(L.lv, log2n), qa);
+    const long long ji = tx_rd_cost(4 * ip, rate2_wave(L.lv2, log2n), qa);
+    int anyl = 0;
+    for (int i = l; i < nn; i += 64) anyl |= L.lv2[i];
+    *idtx = ji < jd && __ballot(anyl != 0) != 0;
+    return jd < ji ? jd : ji;
+}
+__device__ uint32_t recon_luma_wave(BlkLds& L, int log2n, int qidx, bool idtx) {
+    const int l = lane(), n = 1 << log2n, nn = n * n;
+    if (idtx)
+        for (int i = l; i < nn; i += 64) L.lv[i] = L.lv2[i];
+    wsync();
+    const uint32_t summ = dequant_plane<false>(L, log2n, 0, dc_q(qidx), ac_q(qidx), nullptr);
+    wsync();
+    if (l < n) inv_rows_lane(L, log2n, 0, l, idtx && summ);
+    wsync();
+    if (l < n) inv_cols_lane(L, log2n, 0, l, idtx && summ);
+    wsync();
+    return summ;
+}
 __device__ uint32_t recon_chroma_wave(BlkLds& L, int log2n, int qidx) {
     const int l = lane(), ln = log2n - 1, cn = 1 << ln;
     const int qd = dc_q(qidx), qa = ac_q(qidx);
@@ -566,9 +602,14 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
 // colour count of the candidate (0: none) in the low nibble; with av1_chroma_palette the chroma
 // candidate's pair count in the high nibble (pairs into the pal_uv cells, rate into pal_rate_uv).
 // kUv: the session runs with av1_chroma_palette (its own kernels: without it they are what they were).
-template <bool kUv>
+// kCl: the session runs with av1_palette_cluster. A block with more than kPalMax values that the open-loop
+// rule admits (av1_core.h palette_cluster, the same integers here) gets clustered colours: the histogram in
+// hist (256 words of LDS), one distinct value per lane as a group (sum, count), the colour count by wave
+// minima, each merge step one wave minimum over the adjacent pairs' costs; no per-lane arrays.
+// Its pal_rate word carries kPalClusterMark.
+template <bool kUv, bool kCl>
 __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdge& E, uint32_t* seen, uint8_t* map,
-                               uint8_t* col, int* pal_k) {
+                               uint8_t* col, uint32_t* hist, int* pal_k) {
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
     const int l = lane(), log2n = bsl + 2, n = 1 << log2n;
@@ -623,6 +664,68 @@ __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdg
             }
             if (l == 0) A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2;
             *pal_k = k;
+        } else if (kCl && k > kPalMax && k <= kPalClusterValues && palette_cluster_tol(A.frame[1]) >= 1) {
+            for (int i = l; i < 256; i += 64) hist[i] = 0u;
+            wsync();
+            for (int i = l; i < n * n; i += 64)
+                atomicAdd(&hist[f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]], 1u);
+            wsync();
+            // lane i < k (the count of distinct values): the i-th value in ascending order, as a group
+            int val = 256, gs = 0, gn = 1;
+            {
+                int i = l;
+                for (int w = 0; w < 8; w++) {
+                    uint32_t bits = seen[w];
+                    const int cnt = __builtin_popcount(bits);
+                    if (i >= 0 && i < cnt) {
+                        for (; i > 0; i--) bits &= bits - 1u;
+                        val = 32 * w + __builtin_ctz(bits);
+                    }
+                    i -= cnt;   // negative once the lane has its value
+                }
+            }
+            if (l < k) {
+                gn = (int)hist[val];
+                gs = val * gn;
+            }
+            const int above = __shfl_down(val, 1);   // every lane takes part
+            const bool ramp = palette_has_ramp(__ballot(l + 1 < k && above - val <= kPalClusterRampGap));
+            int kc = 0;   // the fewest intervals of width 2 tol over the values, at most kPalMax (wave-uniform)
+            for (int hi = ramp ? 256 : -1, tol = palette_cluster_tol(A.frame[1]); kc < kPalMax; kc++) {
+                const int lo = __builtin_amdgcn_readfirstlane(wmin(val > hi ? val : 256));
+                if (lo == 256) break;
+                hi = lo + 2 * tol;
+            }
+            if (kc >= 2) {
+                for (int cur = k; cur > kc; cur--) {   // the cheapest adjacent pair merges; the groups above move down a lane
+                    const int s2 = __shfl_down(gs, 1), n2 = __shfl_down(gn, 1);
+                    const int key = l + 1 < cur ? (palette_merge_cost(gs, gn, s2, n2) << 6) | l : 0x7fffffff;
+                    const int bi = __builtin_amdgcn_readfirstlane(wmin(key)) & 63;
+                    if (l == bi) {
+                        gs += s2;
+                        gn += n2;
+                    } else if (l > bi && l + 1 < cur) {
+                        gs = s2;
+                        gn = n2;
+                    }
+                }
+                const int mean = palette_cluster_mean(gs, gn);
+                uint64_t C = 0;
+                for (int q = 0; q < kc; q++) C |= (uint64_t)__shfl(mean, q) << (8 * q);
+                for (int i = l; i < n * n; i += 64)
+                    map[i] = (uint8_t)palette_nearest(C, kc, f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]);
+                wsync();
+                int r2 = 0;
+                for (int i = l; i < n * n; i += 64) r2 += palette_rate2_px(map, n, i / n, i % n, kc);
+                r2 = wsum(r2) + palette_rate2_head(kc);
+                const int n8 = (1 << bsl) >> 1;
+                for (int i = l; i < n8 * n8 * 8; i += 64) {
+                    const int cell = i >> 3, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
+                    A.pal[((size_t)ry * g.c8 + cx) * 8 + (i & 7)] = (uint8_t)pal_byte(C, i & 7);
+                }
+                if (l == 0) A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2 | kPalClusterMark;
+                *pal_k = kc;
+            }
         }
         wsync();
     }
@@ -668,12 +771,13 @@ __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdg
 }
 
 // Key frames: intra mode per block from the source edges (one wave per unit).
-template <bool kUv>
+template <bool kUv, bool kCl>
 __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ IntraEdge E[4];
     __shared__ uint32_t pal_seen[4][8];
     __shared__ uint8_t pal_map[4][256], pal_col[4][8];
+    __shared__ uint32_t pal_hist[4][kCl ? 256 : 1];   // av1_palette_cluster: the luma histogram of the wave's block
     if (!A.frame[0]) return;
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
@@ -689,7 +793,7 @@ __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
         unit_block(g, uy, ux, k, r, c);
         BlkInfo b{};
         b.bsl = (uint8_t)bsl;
-        b.mode = (uint8_t)intra_mode_wave<kUv>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
+        b.mode = (uint8_t)intra_mode_wave<kUv, kCl>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], pal_hist[w], &pal_k);
         b.uv_mode = DC_PRED;
         b.pad1 = (uint8_t)pal_k;   // the candidates' colour counts (luma | chroma << 4) ride in the cell until k_av1_intra_rec decides
         set_cells(A, r, c, bsl, b);
@@ -701,12 +805,13 @@ __global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
 // levels (k_av1_inter's cells: inter and not skipped), one wave per unit. The cells stay the inter
 // coding's, so the mode and the colour count travel in A.cand: bit 0 candidate, bits 8..15 the
 // mode, bits 16..19 the palette candidate's colour count, bits 20..23 the chroma palette candidate's.
-template <bool kUv>
+template <bool kUv, bool kCl>
 __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ IntraEdge E[4];
     __shared__ uint32_t pal_seen[4][8];
     __shared__ uint8_t pal_map[4][256], pal_col[4][8];
+    __shared__ uint32_t pal_hist[4][kCl ? 256 : 1];   // av1_palette_cluster: the luma histogram of the wave's block
     if (A.frame[0]) return;
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
@@ -724,7 +829,7 @@ __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
         const BlkInfo b = A.blk[cell];
         int cand = 0;
         if (blk_inter(b) && !blk_skip(b)) {   // wave-uniform
-            const int mode = intra_mode_wave<kUv>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], &pal_k);
+            const int mode = intra_mode_wave<kUv, kCl>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], pal_hist[w], &pal_k);
             cand = 1 | (mode << 8) | (pal_k << 16);
         }
         if (lane() == 0) A.cand[cell] = cand;
@@ -737,7 +842,8 @@ __global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
 // the block is worked out in LDS and becomes the block's coding - reconstruction, levels, level
 // contexts, cells - only where its J plus the mode-bits bias is below the inter coding's
 // (av1_cpu.cpp intra_trial); otherwise nothing is stored.
-// kTools: the session's chroma tools, bit 0 av1_chroma_palette (kUv), bit 1 av1_cfl (kCfl).
+// kTools: the session's tools, bit 0 av1_chroma_palette (kUv), bit 1 av1_cfl (kCfl), bit 2
+// av1_palette_cluster (kCl).
 template <bool kTrial, int kTools>
 __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, int r, int c, int bsl, int qidx, int cand) {
     const FrameArgs& f = A.f;
@@ -747,7 +853,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     const TileRect t = tile_of(g, r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
     const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
-    constexpr bool kUv = (kTools & 1) != 0, kCfl = (kTools & 2) != 0;
+    constexpr bool kUv = (kTools & 1) != 0, kCfl = (kTools & 2) != 0, kCl = (kTools & 4) != 0;
     BlkInfo b{};
     if (kTrial) {
         b.bsl = (uint8_t)bsl;
@@ -786,7 +892,39 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     const int kc = b.pad1 & 15, kuv = kUv ? b.pad1 >> 4 : 0;
     b.pad1 = 0;
     b.pal_n = 0;
-    if (kc && tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx)) < jreg) {
+    const bool clustered = kCl && kc && (A.pal_rate[cell] & kPalClusterMark);   // wave-uniform
+    if (clustered) {
+        // clustered candidate (av1_palette_cluster; av1_cpu.cpp intra_code): every sample on its nearest
+        // colour, luma coded once more against that prediction. The coding standing waits in the chroma
+        // parts of L.b (256 levels) and L.lv2 (256 samples), both dead after code_block_wave.
+        const uint64_t C = pal_load8(A.pal + cell * 8);
+        int16_t* keep_lv = (int16_t*)(L.b + 256);
+        uint8_t* keep_rec = (uint8_t*)(L.lv2 + 256);
+        for (int i = l; i < n * n; i += 64) {
+            keep_lv[i] = L.lv[i];
+            keep_rec[i] = L.pred[i];
+            L.pred[i] = (uint8_t)pal_byte(C, palette_nearest(C, kc, L.src[i]));
+        }
+        wsync();
+        bool idtx;
+        const long long jp = recode_luma_wave(L, F, log2n, qidx, &idtx) +
+                             tx_rd_cost(0, A.pal_rate[cell] & ~kPalClusterMark, ac_q(qidx));
+        if (jp < jreg) {
+            jreg = jp;
+            b.pal_n = (uint8_t)kc;
+            b.mode = DC_PRED;
+            const uint32_t sy = recon_luma_wave(L, log2n, qidx, idtx);
+            b.tx_type = (int16_t)(idtx ? TX_IDTX : TX_DCT_DCT);
+            s = (s & ~0xffu) | sy;
+            s = (s & ~(1u << 24)) | ((s & 0xffffffu) ? (1u << 24) : 0u);
+        } else {
+            for (int i = l; i < n * n; i += 64) {
+                L.lv[i] = keep_lv[i];
+                L.pred[i] = keep_rec[i];
+            }
+            wsync();
+        }
+    } else if (kc && tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx)) < jreg) {
         jreg = tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx));
         b.pal_n = (uint8_t)kc;
         b.mode = DC_PRED;
@@ -1371,14 +1509,15 @@ __device__ __forceinline__ int code_coeffs(WaveTokenSink& w, const CdfContext& c
 
 // Lane-parallel palette_tokens (codec/av1_core.h code_palette_tokens): every sample's
 // colour context depends only on the index map, so lanes rank their samples at once and
-// store each token at its anti-diagonal position.
+// store each token at its anti-diagonal position. kNear: the map is the nearest colour (av1_palette_cluster).
+template <bool kNear>
 __device__ __forceinline__ void code_palette_tokens(WaveTokenSink& w, const CdfContext& cx, const FrameView& v, int r, int c, int bsl,
-                                    int k) {
+                                    int k, BoolTag<kNear>) {
     const int l = lane(), n = 4 << bsl;
     const uint8_t* col = v.pal_at(r, c);
     uint8_t* map = (uint8_t*)w.bits;   // the wave's LDS bit buffer (1 KB), unused here
     for (int i = l; i < n * n; i += 64)
-        map[i] = (uint8_t)palette_index(col, k, v.src_y[(size_t)(r * 4 + i / n) * v.stride_y + c * 4 + i % n]);
+        map[i] = (uint8_t)palette_map_index<kNear>(col, k, v.src_y[(size_t)(r * 4 + i / n) * v.stride_y + c * 4 + i % n]);
     wsync();
     code_ns(w, k, map[0]);
     w.flush();
@@ -1427,7 +1566,7 @@ __device__ __forceinline__ void code_palette_tokens_uv(WaveTokenSink& w, const C
 }
 
 // kTools: bit 0, the session runs with av1_chroma_palette (code_unit's chroma palette syntax compiled
-// in); bit 1, with av1_cfl (the CfL alphas' syntax).
+// in); bit 1, with av1_cfl (the CfL alphas' syntax); bit 2, with av1_palette_cluster (luma index maps by nearest colour).
 template <int kTools>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_av1_tokens(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
@@ -1461,7 +1600,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     const int ux = u % f.mb_w, uy = u / f.mb_w;
     WaveTokenSink sink{A.tok + (size_t)u * kTokCap, 0, kTokCap, 0u, 0, bits_w[w]};
     const TileRect t = tile_of(g, uy * 4, ux * 4);
-    code_unit<WaveTokenSink, (kTools & 1) != 0, (kTools & 2) != 0>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
+    code_unit<WaveTokenSink, (kTools & 1) != 0, (kTools & 2) != 0, (kTools & 4) != 0>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
     sink.flush();
     if (lane() == 0) A.tok_n[u] = sink.n;
 }
@@ -2133,17 +2272,17 @@ void ec_buffers(int tiles, int tile_bytes, int* max_blocks, int* vcap) {
     *vcap = tile_bytes / 4 + 8;
 }
 
-// The kernels that depend on the session's chroma tools (kTools: bit 0 av1_chroma_palette, bit 1
-// av1_cfl): the ones with the candidate, decision and syntax in place of the ones without, the
-// same launches either way. The open-loop mode kernels know the chroma palette only.
+// The kernels that depend on the session's tools (kTools: bit 0 av1_chroma_palette, bit 1 av1_cfl,
+// bit 2 av1_palette_cluster): the ones with the candidate, decision and syntax in place of the ones
+// without, the same launches either way. The open-loop mode kernels know the two palette tools only.
 template <int kTools>
 static void launch_intra(const Av1Args& a, int n, int tiles, hipStream_t s) {
-    hipLaunchKernelGGL(k_av1_intra_modes<(kTools & 1) != 0>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_av1_intra_modes<(kTools & 1) != 0, (kTools & 4) != 0>), dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_intra_rec<kTools>, dim3(tiles), dim3(1024), 0, s, a);
 }
 template <int kTools>
 static void launch_inter_intra(const Av1Args& a, int n, int tiles, hipStream_t s) {
-    hipLaunchKernelGGL(k_av1_cand_modes<(kTools & 1) != 0>, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_av1_cand_modes<(kTools & 1) != 0, (kTools & 4) != 0>), dim3((n + 3) / 4), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_inter_intra<kTools>, dim3(tiles), dim3(1024), 0, s, a);
 }
 template <int kTools>
@@ -2155,7 +2294,11 @@ static void launch_tokens(const Av1Args& a, int n, hipStream_t s) {
         case 0: call(0); break;             \
         case 1: call(1); break;             \
         case 2: call(2); break;             \
-        default: call(3); break;            \
+        case 3: call(3); break;             \
+        case 4: call(4); break;             \
+        case 5: call(5); break;             \
+        case 6: call(6); break;             \
+        default: call(7); break;            \
     }
 
 // Block decisions, reconstruction and the arithmetic-coded tiles: everything the coded
@@ -2164,7 +2307,7 @@ static void launch_code(const Av1Args& a, hipStream_t s) {
     const int n = a.f.mb_w * a.f.mb_h;
     const int tiles = a.geo.tile_cols * a.geo.tile_rows;
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
-    const int tools = (a.chroma_palette ? 1 : 0) | (a.cfl ? 2 : 0);
+    const int tools = (a.chroma_palette ? 1 : 0) | (a.cfl ? 2 : 0) | (a.palette_cluster ? 4 : 0);
 #define SK_INTRA(k) launch_intra<k>(a, n, tiles, s)
     SK_BY_TOOLS(tools, SK_INTRA)
 #undef SK_INTRA

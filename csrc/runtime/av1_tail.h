@@ -39,6 +39,7 @@ struct Av1Tail {
         a.pal_uv = mem.dmalloc<uint8_t>((size_t)geo_.c8 * geo_.r8 * 16);
         a.pal_rate_uv = mem.dmalloc<int>((size_t)geo_.c8 * geo_.r8);
         a.cfl = cfg.av1_cfl > 0;
+        a.palette_cluster = cfg.av1_palette_cluster > 0 && a.palette;
         a.intra_inter = cfg.av1_intra_inter > 0;
         if (a.intra_inter) {   // av1_gpu.h: the inter coding's J, the intra candidates and their count per tile
             a.jinter = mem.dmalloc<long long>((size_t)geo_.c8 * geo_.r8);
@@ -163,6 +164,7 @@ struct Av1Tail {
             {"av1_geo", &geo_, (int64_t)sizeof(geo_), true},
             {"blk", v.blk, (int64_t)(blks * sizeof(av1::BlkInfo))},
             {"levels", v.lev, nmb * av1::gpu::kLevPerUnit * 2},
+            {"pal", v.pal, blks * 8},          // meaningful in cells whose PaletteSizeY is nonzero
             {"pal_uv", v.pal_uv, blks * 16},   // meaningful in cells whose PaletteSizeUV is nonzero
             {"tok_n", v.tok_n, nmb * 4},
             {"tokc", v.tokc, tiles * v.tile_tok_cap * 4},

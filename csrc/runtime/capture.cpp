@@ -125,6 +125,7 @@ class CaptureSession {
                 e.av1_intra_inter = e.codec == 2 && s.av1_intra_inter > 0 ? 1 : 0;
                 e.av1_chroma_palette = e.codec == 2 && s.av1_chroma_palette > 0 ? 1 : 0;
                 e.av1_cfl = e.codec == 2 && s.av1_cfl > 0 ? 1 : 0;
+                e.av1_palette_cluster = e.codec == 2 && s.av1_palette_cluster > 0 ? 1 : 0;
                 if (const char* err = h264::ltr_config_error(e)) throw std::runtime_error(err);
                 ecfg_ = e;
                 enc_.reset(backend ? create_hip_backend(e, s.device) : create_cpu_backend(e));

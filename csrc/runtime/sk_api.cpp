@@ -84,6 +84,7 @@ DebugBuf codec_debug(hevc::CpuHevcEncoder& e, const std::string& s) {
 DebugBuf codec_debug(av1::CpuAv1Encoder& e, const std::string& s) {
     if (s == "blk") return bytes_of(e.blk);
     if (s == "levels") return bytes_of(e.lev);
+    if (s == "pal") return bytes_of(e.pal);         // meaningful in cells whose PaletteSizeY is nonzero
     if (s == "pal_uv") return bytes_of(e.pal_uv);   // meaningful in cells whose PaletteSizeUV is nonzero
     if (s == "av1_geo") return {&e.geo, (int64_t)sizeof(av1::Av1Geo)};
     if (s == "av1_qidx") return {&e.fp.qidx, 4};
@@ -236,6 +237,7 @@ h264::EncoderConfig to_config(const sk_h264_config* c) {
     e.av1_intra_inter = c->codec == 2 && c->av1_intra_inter > 0 ? 1 : 0;
     e.av1_chroma_palette = c->codec == 2 && c->av1_chroma_palette > 0 ? 1 : 0;
     e.av1_cfl = c->codec == 2 && c->av1_cfl > 0 ? 1 : 0;
+    e.av1_palette_cluster = c->codec == 2 && c->av1_palette_cluster > 0 ? 1 : 0;
     if (e.codec >= 1) {   // HEVC / AV1: full-frame pictures, slices of whole CTB rows, one reference
         e.aq_strength = 0;   // no cu_qp_delta in this HEVC profile setup
         e.fullframe = 1;

@@ -35,6 +35,8 @@ typedef struct sk_h264_config {
     int32_t av1_chroma_palette;     // AV1: exact chroma palettes on intra blocks, where luma palettes may occur (> 0 on);
                                     // other codecs ignore it
     int32_t av1_cfl;                // AV1: chroma from luma (UV_CFL_PRED) on intra blocks (> 0 on); other codecs ignore it
+    int32_t av1_palette_cluster;    // AV1: clustered luma palettes with a residual on intra blocks with more than 8 luma
+                                    // values, where luma palettes may occur (> 0 on); other codecs ignore it
 } sk_h264_config;
 
 typedef struct sk_packet {
@@ -179,6 +181,7 @@ typedef struct sk_capture_settings {
     int32_t av1_intra_inter;   // AV1 sessions (output_mode 3): intra blocks and luma palettes in inter frames (> 0 on)
     int32_t av1_chroma_palette;   // AV1 sessions: exact chroma palettes on intra blocks (> 0 on)
     int32_t av1_cfl;           // AV1 sessions: chroma from luma on intra blocks (> 0 on)
+    int32_t av1_palette_cluster;   // AV1 sessions: clustered luma palettes with a residual on intra blocks (> 0 on)
 } sk_capture_settings;
 
 typedef struct sk_stripe_result {

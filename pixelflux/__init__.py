@@ -64,6 +64,7 @@ def default_settings(width: int = 1920, height: int = 1080, **kw) -> CaptureSett
     s.av1_intra_inter = 0   # AV1 sessions: intra blocks and luma palettes in inter frames (off)
     s.av1_chroma_palette = 0   # AV1 sessions: exact chroma palettes on intra blocks (off)
     s.av1_cfl = 0   # AV1 sessions: chroma from luma on intra blocks (off)
+    s.av1_palette_cluster = 0   # AV1 sessions: clustered luma palettes with a residual on intra blocks (off)
     for k, v in kw.items():
         if isinstance(v, str):
             v = v.encode()

@@ -37,6 +37,7 @@ class SkH264Config(ctypes.Structure):
         ("tile_cols_log2", ctypes.c_int32), ("tile_rows_log2", ctypes.c_int32),
         ("rc_mode", ctypes.c_int32), ("bitrate_kbps", ctypes.c_int32), ("ltr_slots", ctypes.c_int32),
         ("av1_intra_inter", ctypes.c_int32), ("av1_chroma_palette", ctypes.c_int32), ("av1_cfl", ctypes.c_int32),
+        ("av1_palette_cluster", ctypes.c_int32),
     ]
 
 
@@ -72,6 +73,7 @@ class SkCaptureSettings(ctypes.Structure):
         ("h264_rc_mode", ctypes.c_int32), ("h264_bitrate_kbps", ctypes.c_int32),
         ("h264_me_full", ctypes.c_int32), ("h264_ltr_slots", ctypes.c_int32),
         ("av1_intra_inter", ctypes.c_int32), ("av1_chroma_palette", ctypes.c_int32), ("av1_cfl", ctypes.c_int32),
+        ("av1_palette_cluster", ctypes.c_int32),
     ]
 
 
@@ -343,8 +345,8 @@ class H264Encoder:
                  aq_strength: float = 0.0, subpel: bool = True, intra4x4: bool = False,
                  tile_cols_log2: int = -1, tile_rows_log2: int = -1, rate_control: str = "cqp",
                  bitrate_kbps: int = 0, ltr_slots: int = 0, av1_intra_inter: bool = False,
-                 av1_chroma_palette: bool = False, av1_cfl: bool = False):
-        """av1_intra_inter, av1_chroma_palette, av1_cfl: AV1 only (Av1Encoder(intra_inter=..., chroma_palette=..., cfl=...)), the other codecs ignore them. ltr_slots: long-term reference cache, pictures kept per stream (stripe, or the picture in
+                 av1_chroma_palette: bool = False, av1_cfl: bool = False, av1_palette_cluster: bool = False):
+        """av1_intra_inter, av1_chroma_palette, av1_cfl, av1_palette_cluster: AV1 only (Av1Encoder(intra_inter=..., chroma_palette=..., cfl=..., palette_cluster=...)), the other codecs ignore them. ltr_slots: long-term reference cache, pictures kept per stream (stripe, or the picture in
         full-frame mode) for content that comes back, 0 = off, 1..8 (AV1: 1..7); H.264: not with
         num_refs > 1. aq_strength: MB-level adaptive QP (h264_mb.h aq_offset), 1.0 = x264 aq-mode 1
         strength; 0 = constant QP per slice (x264 ultrafast behaviour). deblock: True / False,
@@ -365,7 +367,8 @@ class H264Encoder:
                                 RC_MODES[rate_control], int(bitrate_kbps), int(ltr_slots),
                                 1 if av1_intra_inter and codec == "av1" else 0,
                                 1 if av1_chroma_palette and codec == "av1" else 0,
-                                1 if av1_cfl and codec == "av1" else 0)
+                                1 if av1_cfl and codec == "av1" else 0,
+                                1 if av1_palette_cluster and codec == "av1" else 0)
         if codec not in ("h264", "hevc", "av1"):
             raise ValueError("codec must be 'h264', 'hevc' or 'av1'")
         self.codec = codec
@@ -650,16 +653,24 @@ class Av1Encoder(H264Encoder):
     costs less by RD than the chroma coding standing, UV_DC_PRED + DCT or a chroma palette: content
     of one hue whose brightness varies (anti-aliased coloured text, gradients, icons, images). It
     does not depend on allow_screen_content_tools. Off (the default), every byte is what it was
-    without the option."""
+    without the option.
+
+    palette_cluster = True lets a fully visible intra block whose source luma holds more than 8
+    distinct values (anti-aliased text) code its luma as a palette of 2..8 clustered colours, each
+    sample on its nearest colour, plus a DCT_DCT or IDTX residual against that prediction, where
+    that costs less by RD than the transform path (av1_core.h palette_cluster). Blocks with 2..8
+    values keep the exact palette. Off (the default), every byte is what it was without the option."""
 
     def __init__(self, width: int, height: int, *, intra_inter: bool = False, chroma_palette: bool = False,
-                 cfl: bool = False, **kw):
+                 cfl: bool = False, palette_cluster: bool = False, **kw):
         kw.pop("fullframe", None)
         kw.pop("av1_intra_inter", None)
         kw.pop("av1_chroma_palette", None)
         kw.pop("av1_cfl", None)
+        kw.pop("av1_palette_cluster", None)
         super().__init__(width, height, codec="av1", fullframe=True, av1_intra_inter=bool(intra_inter),
-                         av1_chroma_palette=bool(chroma_palette), av1_cfl=bool(cfl), **kw)
+                         av1_chroma_palette=bool(chroma_palette), av1_cfl=bool(cfl),
+                         av1_palette_cluster=bool(palette_cluster), **kw)
 
 
 class JpegEncoder(H264Encoder):

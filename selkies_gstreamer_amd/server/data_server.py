@@ -211,6 +211,12 @@ def _av1_cfl_from_env() -> int:
     return int(os.environ.get("SELKIES_AV1_CFL", "").strip().lower() in ("1", "true", "yes", "on"))
 
 
+def _av1_palette_cluster_from_env() -> int:
+    """SELKIES_AV1_PALETTE_CLUSTER: clustered luma palettes with a residual on the intra blocks of AV1
+    (svtav1enc) sessions (csrc/codec/av1_core.h), 1 / true / yes / on = on, default off."""
+    return int(os.environ.get("SELKIES_AV1_PALETTE_CLUSTER", "").strip().lower() in ("1", "true", "yes", "on"))
+
+
 def files_listing_html(path: str, rel: str) -> str:
     """HTML listing of one directory of the download area: sub-directories first,
     then files with their sizes; names are escaped and links percent-encoded."""
@@ -911,6 +917,7 @@ class DataStreamingServer:
             cs.av1_intra_inter = _av1_intra_inter_from_env() if cs.output_mode == 3 else 0
             cs.av1_chroma_palette = _av1_chroma_palette_from_env() if cs.output_mode == 3 else 0
             cs.av1_cfl = _av1_cfl_from_env() if cs.output_mode == 3 else 0
+            cs.av1_palette_cluster = _av1_palette_cluster_from_env() if cs.output_mode == 3 else 0
         cs.use_paint_over_quality = int(bool(p["use_paint_over_quality"]))
         cs.paint_over_trigger_frames, cs.damage_block_threshold, cs.damage_block_duration = 15, 10, 20
         cs.use_cpu = int(bool(p["use_cpu"]))
