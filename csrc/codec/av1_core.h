@@ -102,6 +102,62 @@ SK_HD int pal_nuv(const BlkInfo& b) { return b.pal_n >> 4; }
 SK_HD int cfl_alpha_u(const BlkInfo& b) { return b.mv_row; }
 SK_HD int cfl_alpha_v(const BlkInfo& b) { return b.mv_col; }
 
+// The session's screen-content tools as one word, derived once from the configuration
+// (av1_encoder.h session_tools) and carried by both back ends (CpuAv1Encoder::tools, Av1Args::tools).
+// Bits 0..2 are the template index kTools of the kernels that know the tools (k_av1_intra_rec,
+// k_av1_inter_intra, k_av1_tokens; the open-loop mode kernels take it without the CfL bit);
+// kToolIntraInter is a run-time switch and never part of that index. The two palette tools are
+// set only in sessions whose palettes are enabled, so no reader asks for that again.
+enum Tools : int {
+    kToolUv = 1,           // av1_chroma_palette: exact chroma palettes where luma palettes may occur
+    kToolCfl = 2,          // av1_cfl: chroma from luma on every intra block
+    kToolCluster = 4,      // av1_palette_cluster: clustered luma palettes with a residual
+    kToolIntraInter = 8,   // av1_intra_inter: intra blocks (with the tools above) in inter frames
+    kToolsKernel = kToolUv | kToolCfl | kToolCluster,
+};
+SK_HD constexpr bool has_uv(int tools) { return (tools & kToolUv) != 0; }
+SK_HD constexpr bool has_cfl(int tools) { return (tools & kToolCfl) != 0; }
+SK_HD constexpr bool has_cluster(int tools) { return (tools & kToolCluster) != 0; }
+SK_HD constexpr bool has_intra_inter(int tools) { return (tools & kToolIntraInter) != 0; }
+// allow_screen_content_tools of a frame: palettes wherever intra blocks may occur.
+SK_HD constexpr bool frame_screen(bool key, int tools, bool palette) { return (key || has_intra_inter(tools)) && palette; }
+
+// Plane p of a block's working set (levels, samples; raster per plane): luma at 0, U at 256, V at 320.
+SK_HD constexpr int plane_off(int p) { return p == 0 ? 0 : (p == 1 ? 256 : 320); }
+
+// An open-loop intra candidate between the mode kernels and the reconstruction: bit 0 the block is a
+// candidate, bits 8..15 its mode, bits 16..19 the luma palette candidate's colour count, bits 20..23
+// the chroma palette candidate's pair count (0: none). Inter frames: k_av1_cand_modes -> A.cand ->
+// k_av1_inter_intra. Key frames: the cell carries the mode, and bits 16..23 ride in BlkInfo.pad1 until
+// k_av1_intra_rec decides (cand_pad1 / cand_of_cell).
+SK_HD int cand_pack(int mode, int ky, int kuv) { return 1 | (mode << 8) | (ky << 16) | (kuv << 20); }
+SK_HD bool cand_is(int w) { return (w & 1) != 0; }
+SK_HD int cand_mode(int w) { return (w >> 8) & 255; }
+SK_HD int cand_ky(int w) { return (w >> 16) & 15; }
+SK_HD int cand_kuv(int w) { return (w >> 20) & 15; }
+SK_HD uint8_t cand_pad1(int w) { return (uint8_t)(w >> 16); }
+SK_HD int cand_of_cell(const BlkInfo& b) { return cand_pack(b.mode, b.pad1 & 15, b.pad1 >> 4); }
+
+// A block's level summary (code_block_wave): bytes 0..2 the per-plane summaries (cul | dc << 6, the
+// level contexts), bit 24 any plane keeps a level, bit 25 the luma transform is IDTX. A plane with a
+// level has a nonzero summary, so the setters derive bit 24 from the three bytes.
+constexpr uint32_t kSummLuma = 0xffu, kSummChroma = 0xffff00u, kSummAny = 1u << 24, kSummIdtx = 1u << 25;
+SK_HD uint32_t summ_pack(uint32_t planes, bool idtx) {
+    return planes | (planes ? kSummAny : 0u) | (idtx && planes ? kSummIdtx : 0u);   // no levels: DCT_DCT
+}
+SK_HD uint8_t summ_plane(uint32_t s, int p) { return (uint8_t)((s >> (8 * p)) & 0xff); }
+SK_HD bool summ_any(uint32_t s) { return (s & kSummAny) != 0; }
+SK_HD bool summ_idtx(uint32_t s) { return (s & kSummIdtx) != 0; }
+SK_HD bool summ_chroma(uint32_t s) { return (s & kSummChroma) != 0; }
+SK_HD uint32_t summ_with(uint32_t s, uint32_t mask, uint32_t planes) {
+    s = (s & ~(mask | kSummAny)) | planes;
+    return s | ((s & (kSummLuma | kSummChroma)) ? kSummAny : 0u);
+}
+SK_HD uint32_t summ_set_luma(uint32_t s, uint32_t sy) { return summ_with(s, kSummLuma, sy); }
+SK_HD uint32_t summ_set_chroma(uint32_t s, uint32_t suv) { return summ_with(s, kSummChroma, suv); }
+SK_HD uint32_t summ_clear_luma(uint32_t s) { return summ_with(s, kSummLuma, 0u); }
+SK_HD uint32_t summ_clear_chroma(uint32_t s) { return summ_with(s, kSummChroma, 0u); }
+
 // ---------------------------------------------------------------------------------
 // Transforms. Forward: encoder choice, an integer DCT-II scaled to 8x the
 // orthonormal transform (the coefficient domain of AV1's 4/8/16-point transforms,
@@ -1071,9 +1127,9 @@ struct FrameView {
     // levels of the block at mi (r, c) of size bsl in plane p (raster [row][col])
     SK_HD const int16_t* levels(int r, int c, int bsl, int p) const {
         const int16_t* u = lev + ((size_t)(r >> 2) * unit_w + (c >> 2)) * 384;
-        if (bsl >= 2) return u + (p == 0 ? 0 : (p == 1 ? 256 : 320));
+        if (bsl >= 2) return u + plane_off(p);
         const int k = ((r >> 1) & 1) * 2 + ((c >> 1) & 1);
-        return u + (p == 0 ? 64 * k : (p == 1 ? 256 + 16 * k : 320 + 16 * k));
+        return u + plane_off(p) + (p == 0 ? 64 : 16) * k;
     }
     // selects without indexing lctx / lctx_w by a run-time plane: an indexed member array
     // keeps the whole view in GPU scratch memory
@@ -1504,6 +1560,12 @@ SK_HD int palette_rate2_px(const uint8_t* map, int n, int i, int j, int k) {
     if (i == 0 && j == 0) return 2 * ceil_log2(k);
     const bool rep = (j > 0 && map[i * n + j - 1] == x) || (i > 0 && map[(i - 1) * n + j] == x);
     return rep ? 1 : 2 + 2 * ceil_log2(k);
+}
+// The whole map after `head` (palette_rate2_head, or palette_uv_rate2_head for a chroma map).
+SK_HD int palette_map_rate2(const uint8_t* map, int n, int k, int head) {
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) head += palette_rate2_px(map, n, i, j, k);
+    return head;
 }
 
 // ---------------------------------------------------------------------------------

@@ -203,11 +203,8 @@ CpuAv1Encoder::CpuAv1Encoder(const h264::EncoderConfig& cfg, int tcl, int trl) :
     lctx_w[1] = lctx_w[2] = geo.mi_cols >> 1;
     pal.assign((size_t)geo.c8 * geo.r8 * 8, 0);
     pal_uv.assign((size_t)geo.c8 * geo.r8 * 16, 0);
-    chroma_palette = cfg.av1_chroma_palette > 0;
-    cfl = cfg.av1_cfl > 0;
-    palette_cluster = cfg.av1_palette_cluster > 0;
+    tools = session_tools(cfg, palette_on);
     jinter.assign((size_t)geo.c8 * geo.r8, 0);
-    intra_inter = cfg.av1_intra_inter > 0;
     lctx_h[1] = lctx_h[2] = geo.mi_rows >> 1;
     for (int p = 0; p < 3; p++) lctx[p].assign((size_t)lctx_w[p] * lctx_h[p], 0);
     level_idx = choose_level_idx(W, H, cfg.fps);
@@ -232,9 +229,9 @@ void CpuAv1Encoder::set_lctx(int plane, int x4, int y4, int n4, uint8_t v) {
 int16_t* CpuAv1Encoder::unit_lev(int r, int c, int bsl, int plane) const {
     const int ux = c >> 2, uy = r >> 2;
     int16_t* u = const_cast<int16_t*>(&lev[((size_t)uy * fe.g.mb_w + ux) * kLevPerUnit]);
-    if (bsl >= 2) return u + (plane == 0 ? 0 : (plane == 1 ? 256 : 320));
+    if (bsl >= 2) return u + plane_off(plane);
     const int k = ((r >> 1) & 1) * 2 + ((c >> 1) & 1);
-    return u + (plane == 0 ? 64 * k : (plane == 1 ? 256 + 16 * k : 320 + 16 * k));
+    return u + plane_off(plane) + (plane == 0 ? 64 : 16) * k;
 }
 
 static uint8_t level_summary(const int16_t* lv, int nn) {
@@ -347,186 +344,197 @@ int intra_mode_decision(const uint8_t* src, int stride, int x, int y, int log2n,
     return best;
 }
 
+// What the steps of intra_code share about the block they decide.
+struct CpuAv1Encoder::IntraWork {
+    int log2n, n, cn;
+    const uint8_t* src[3];   // the block's source samples per plane, pitch stride[p]
+    int stride[3];
+    bool palettes;           // palettes may occur: allow_screen_content_tools, and the block is fully visible
+    uint8_t pred[384];       // the prediction standing, plane p at plane_off(p), pitch n / cn
+    IntraEdge e[3];
+};
+
+// Exact luma palette (the source's 2..kPalMax values, no residual) against the transform path.
+// Returns the candidate's colour count, taken or not (0: the block has none).
+int CpuAv1Encoder::try_luma_palette(IntraWork& w, IntraCoding& o) const {
+    const int n = w.n, k = palette_colors(w.src[0], w.stride[0], n, o.col);
+    if (!k) return 0;
+    uint8_t map[256];
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) map[i * n + j] = (uint8_t)palette_index(o.col, k, w.src[0][(size_t)i * w.stride[0] + j]);
+    const long long jp = tx_rd_cost(0, palette_map_rate2(map, n, k, palette_rate2_head(k)), ac_q(fp.qidx));
+    if (jp < o.jy) {
+        o.jy = jp;
+        o.b.pal_n = (uint8_t)k;
+        o.b.mode = DC_PRED;
+        o.b.tx_type = TX_DCT_DCT;
+        memset(o.lev, 0, sizeof(int16_t) * n * n);
+        for (int i = 0; i < n; i++) memcpy(&w.pred[i * n], w.src[0] + (size_t)i * w.stride[0], (size_t)n);
+    }
+    return k;
+}
+
+// Clustered luma palette (av1_palette_cluster, av1_core.h): a block with more than kPalMax values that
+// the open-loop rule admits; the palette prediction codes luma once more, DCT_DCT or IDTX, against the
+// J standing.
+void CpuAv1Encoder::try_luma_cluster(IntraWork& w, IntraCoding& o) const {
+    const int n = w.n;
+    uint16_t hist[256] = {0};
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) hist[w.src[0][(size_t)i * w.stride[0] + j]]++;
+    const int kc = palette_cluster(hist, palette_cluster_tol(fp.qidx), o.col);
+    if (!kc) return;
+    uint8_t map[256], pp[256];
+    int16_t ld[256], lid[256];
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            map[i * n + j] = (uint8_t)palette_map_index<true>(o.col, kc, w.src[0][(size_t)i * w.stride[0] + j]);
+            pp[i * n + j] = o.col[map[i * n + j]];
+        }
+    const long long jd = quant_block(w.src[0], w.stride[0], pp, w.log2n, fp.qidx, true, TX_DCT_DCT, ld);
+    const long long ji = quant_block(w.src[0], w.stride[0], pp, w.log2n, fp.qidx, true, TX_IDTX, lid);
+    const long long jp = (jd < ji ? jd : ji) + tx_rd_cost(0, palette_map_rate2(map, n, kc, palette_rate2_head(kc)), ac_q(fp.qidx));
+    if (jp < o.jy) {
+        o.jy = jp;
+        o.b.pal_n = (uint8_t)kc;
+        o.b.mode = DC_PRED;
+        o.b.tx_type = (int16_t)(ji < jd && any_nonzero(lid, n * n) ? TX_IDTX : TX_DCT_DCT);
+        memcpy(o.lev, o.b.tx_type == TX_IDTX ? lid : ld, sizeof(int16_t) * n * n);
+        memcpy(w.pred, pp, (size_t)n * n);
+    }
+}
+
+// Chroma palette (av1_chroma_palette): the exact (U, V) pairs of the source against both DCT planes.
+void CpuAv1Encoder::try_chroma_palette(IntraWork& w, IntraCoding& o) const {
+    const int cn = w.cn, sc = w.stride[1];
+    const uint8_t *su = w.src[1], *sv = w.src[2];
+    const int kuv = palette_colors_uv(su, sv, sc, cn, &o.col_u, &o.col_v);
+    if (!kuv) return;
+    uint8_t map[64];
+    for (int i = 0; i < cn; i++)
+        for (int j = 0; j < cn; j++)
+            map[i * cn + j] = (uint8_t)palette_index_uv(o.col_u, o.col_v, kuv, su[(size_t)i * sc + j], sv[(size_t)i * sc + j]);
+    const long long jp = tx_rd_cost(0, palette_map_rate2(map, cn, kuv, palette_uv_rate2_head(o.col_u, o.col_v, kuv)), ac_q(fp.qidx));
+    if (jp < o.jc) {
+        o.jc = jp;
+        o.b.pal_n = (uint8_t)(o.b.pal_n | (kuv << 4));
+        for (int p = 1; p < 3; p++) {
+            memset(o.lev + plane_off(p), 0, sizeof(int16_t) * cn * cn);
+            for (int i = 0; i < cn; i++) memcpy(&w.pred[plane_off(p) + i * cn], w.src[p] + (size_t)i * sc, (size_t)cn);
+        }
+    }
+}
+
+// Chroma from luma (av1_cfl, av1_core.h) on a block whose UV_DC_PRED coding kept a chroma level: where
+// the luma reconstruction (o.rec) varies, one alpha per plane, both planes coded again, against the
+// chroma J standing.
+void CpuAv1Encoder::try_cfl(IntraWork& w, IntraCoding& o) const {
+    const int n = w.n, cn = w.cn, cl2 = w.log2n - 1, sc = w.stride[1];
+    int ac[64], sum = 0;
+    bool flat = true;
+    for (int i = 0; i < cn; i++)
+        for (int j = 0; j < cn; j++) sum += ac[i * cn + j] = cfl_luma(o.rec, n, i, j);
+    const int avg = cfl_avg(sum, cl2);
+    for (int k = 0; k < cn * cn; k++) flat &= (ac[k] -= avg) == 0;
+    if (flat) return;
+    const int dc[2] = {intra_dc(w.e[1], cl2), intra_dc(w.e[2], cl2)};
+    int alpha[2];
+    long long sxx = 0;
+    for (int k = 0; k < cn * cn; k++) sxx += (long long)ac[k] * ac[k];
+    for (int p = 0; p < 2; p++) {
+        const uint8_t* sp = w.src[1 + p];
+        long long sxy = 0;
+        for (int i = 0; i < cn; i++)
+            for (int j = 0; j < cn; j++) sxy += (long long)ac[i * cn + j] * ((int)sp[(size_t)i * sc + j] - dc[p]);
+        const int a0 = cfl_alpha0(sxx, sxy);
+        int best = 0x7fffffff;
+        alpha[p] = 0;
+        for (int q = 0; q < 3; q++) {
+            const int a = cfl_cand(a0, sxy, q);
+            int sse = 0;
+            for (int i = 0; i < cn; i++)
+                for (int j = 0; j < cn; j++) {
+                    const int e = (int)sp[(size_t)i * sc + j] - cfl_px(dc[p], a, ac[i * cn + j]);
+                    sse += e * e;
+                }
+            if (sse < best) {
+                best = sse;
+                alpha[p] = a;
+            }
+        }
+    }
+    if (!alpha[0] && !alpha[1]) return;
+    uint8_t pc[2][64];
+    int16_t lc[2][64];
+    long long j = tx_rd_cost(0, cfl_rate2(alpha[0], alpha[1]), ac_q(fp.qidx));
+    for (int p = 0; p < 2; p++) {
+        for (int k = 0; k < cn * cn; k++) pc[p][k] = (uint8_t)cfl_px(dc[p], alpha[p], ac[k]);
+        j += quant_block(w.src[1 + p], sc, pc[p], cl2, fp.qidx, true, TX_DCT_DCT, lc[p]);
+    }
+    if (j < o.jc) {
+        o.jc = j;
+        o.b.uv_mode = UV_CFL_PRED;
+        o.b.pal_n &= 15;
+        o.b.mv_row = (int16_t)alpha[0];
+        o.b.mv_col = (int16_t)alpha[1];
+        for (int p = 0; p < 2; p++) {
+            memcpy(w.pred + plane_off(1 + p), pc[p], (size_t)cn * cn);
+            memcpy(o.lev + plane_off(1 + p), lc[p], sizeof(int16_t) * cn * cn);
+        }
+    }
+}
+
 // One intra block in `mode` (the open-loop decision), predicted from the reconstruction of its
-// neighbours as it stands: levels, reconstruction and the J of the coding (luma: the cheapest of
-// DCT_DCT, IDTX and the exact palette; chroma: UV_DC_PRED, DCT_DCT, or with av1_chroma_palette the
-// exact palette, or with av1_cfl UV_CFL_PRED, DCT_DCT, where that is cheaper) into `o`. Changes no state.
+// neighbours as it stands: levels, reconstruction and the J of the coding into `o`. Luma: the cheaper
+// of DCT_DCT and IDTX, then the palette candidates; chroma: UV_DC_PRED, DCT_DCT, then the chroma
+// palette and CfL. The same chain, under the same names, as intra_rec_block of the kernels. Changes
+// no state.
 void CpuAv1Encoder::intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const {
     const h264::Geometry& g = fe.g;
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
-    const int log2n = bsl + 2, n = 1 << log2n;
-    const int x = c * 4, y = r * 4;
-    BlkInfo b{};
-    b.bsl = (uint8_t)bsl;
-    b.mode = (uint8_t)mode;
-    b.uv_mode = DC_PRED;
-    int16_t* ly = o.lev;
-    IntraEdge ey;
-    intra_edges(fe.rec[0].data(), g.stride_y, x, y, n, au, al, geo.mi_cols * 4 - 1, geo.mi_rows * 4 - 1, ey);
-    uint8_t py[256];
-    intra_predict(ey, b.mode, log2n, py);
-    // luma transform type: DCT_DCT or IDTX (screen content: sharp text codes as samples), by RD cost
-    int16_t lid[256];
-    const uint8_t* sy = &fe.src[0][(size_t)y * g.stride_y + x];
-    const long long jd = quant_block(sy, g.stride_y, py, log2n, fp.qidx, true, TX_DCT_DCT, ly);
-    const long long ji = quant_block(sy, g.stride_y, py, log2n, fp.qidx, true, TX_IDTX, lid);
-    b.tx_type = (int16_t)(ji < jd && any_nonzero(lid, n * n) ? TX_IDTX : TX_DCT_DCT);
-    if (b.tx_type == TX_IDTX) memcpy(ly, lid, sizeof(int16_t) * n * n);
-    b.pal_n = 0;
-    o.jy = jd < ji ? jd : ji;
-    uint8_t* col = o.col;
-    memset(col, 0, kPalMax);
-    const bool visible = r + (1 << bsl) <= geo.mi_rows && c + (1 << bsl) <= geo.mi_cols;
-    const int k = fp.screen && visible ? palette_colors(sy, g.stride_y, n, col) : 0;
-    if (k) {   // exact palette vs the transform path (J of the levels just chosen)
-        uint8_t map[256];
-        int rate2 = palette_rate2_head(k);
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) map[i * n + j] = (uint8_t)palette_index(col, k, sy[(size_t)i * g.stride_y + j]);
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) rate2 += palette_rate2_px(map, n, i, j, k);
-        if (tx_rd_cost(0, rate2, ac_q(fp.qidx)) < o.jy) {
-            o.jy = tx_rd_cost(0, rate2, ac_q(fp.qidx));
-            b.pal_n = (uint8_t)k;
-            b.mode = DC_PRED;
-            b.tx_type = TX_DCT_DCT;
-            memset(ly, 0, sizeof(int16_t) * n * n);
-            for (int i = 0; i < n; i++) memcpy(&py[i * n], sy + (size_t)i * g.stride_y, (size_t)n);
-        }
+    const int x = c * 4, y = r * 4, cx = x >> 1, cy = y >> 1;
+    IntraWork w;
+    w.log2n = bsl + 2;
+    w.n = 1 << w.log2n;
+    w.cn = w.n >> 1;
+    const int log2n = w.log2n, n = w.n, cl2 = log2n - 1, cn = w.cn;
+    for (int p = 0; p < 3; p++) {
+        w.stride[p] = p ? g.stride_c : g.stride_y;
+        w.src[p] = &fe.src[p][p ? (size_t)cy * g.stride_c + cx : (size_t)y * g.stride_y + x];
     }
-    // clustered palette (av1_palette_cluster, av1_core.h): a block with more than kPalMax values that the
-    // open-loop rule admits; the palette prediction codes luma once more, DCT_DCT or IDTX, against the J standing
-    if (palette_cluster && fp.screen && visible && !k) {
-        uint16_t hist[256] = {0};
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < n; j++) hist[sy[(size_t)i * g.stride_y + j]]++;
-        const int kc = sk::av1::palette_cluster(hist, palette_cluster_tol(fp.qidx), col);
-        if (kc) {
-            uint8_t map[256], pp[256];
-            int16_t ld[256];
-            int rate2 = palette_rate2_head(kc);
-            for (int i = 0; i < n; i++)
-                for (int j = 0; j < n; j++) {
-                    map[i * n + j] = (uint8_t)palette_map_index<true>(col, kc, sy[(size_t)i * g.stride_y + j]);
-                    pp[i * n + j] = col[map[i * n + j]];
-                }
-            for (int i = 0; i < n; i++)
-                for (int j = 0; j < n; j++) rate2 += palette_rate2_px(map, n, i, j, kc);
-            const long long jd2 = quant_block(sy, g.stride_y, pp, log2n, fp.qidx, true, TX_DCT_DCT, ld);
-            const long long ji2 = quant_block(sy, g.stride_y, pp, log2n, fp.qidx, true, TX_IDTX, lid);
-            const long long jp = (jd2 < ji2 ? jd2 : ji2) + tx_rd_cost(0, rate2, ac_q(fp.qidx));
-            if (jp < o.jy) {
-                o.jy = jp;
-                b.pal_n = (uint8_t)kc;
-                b.mode = DC_PRED;
-                b.tx_type = (int16_t)(ji2 < jd2 && any_nonzero(lid, n * n) ? TX_IDTX : TX_DCT_DCT);
-                memcpy(ly, b.tx_type == TX_IDTX ? lid : ld, sizeof(int16_t) * n * n);
-                memcpy(py, pp, (size_t)n * n);
-            }
-        }
-    }
-    bool nz = recon_block(ly, log2n, fp.qidx, true, b.tx_type, py, o.rec, n);
-    // chroma: UV_DC_PRED first. Every other UV mode but UV_CFL_PRED (below) implies an ADST-family
-    // chroma transform (Mode_To_Txfm, §7.13.3 compute_tx_type); this encoder's transforms are DCT_DCT.
-    const int cl2 = log2n - 1, cn = n >> 1, cx = x >> 1, cy = y >> 1;
-    IntraEdge eu, ev;
-    intra_edges(fe.rec[1].data(), g.stride_c, cx, cy, cn, au, al, geo.mi_cols * 2 - 1, geo.mi_rows * 2 - 1, eu);
-    intra_edges(fe.rec[2].data(), g.stride_c, cx, cy, cn, au, al, geo.mi_cols * 2 - 1, geo.mi_rows * 2 - 1, ev);
-    uint8_t bu[64], bv[64];
-    intra_predict(eu, DC_PRED, cl2, bu);
-    intra_predict(ev, DC_PRED, cl2, bv);
-    int16_t* lu = o.lev + 256;
-    int16_t* lvv = o.lev + 320;
-    o.jc = quant_block(&fe.src[1][(size_t)cy * g.stride_c + cx], g.stride_c, bu, cl2, fp.qidx, true, TX_DCT_DCT, lu);
-    o.jc += quant_block(&fe.src[2][(size_t)cy * g.stride_c + cx], g.stride_c, bv, cl2, fp.qidx, true, TX_DCT_DCT, lvv);
-    const bool dc_kept = any_nonzero(lu, cn * cn) || any_nonzero(lvv, cn * cn);   // before a palette clears them
-    // chroma palette (av1_chroma_palette): the exact (U, V) pairs of the source vs both DCT planes
-    const uint8_t* su = &fe.src[1][(size_t)cy * g.stride_c + cx];
-    const uint8_t* sv = &fe.src[2][(size_t)cy * g.stride_c + cx];
+    w.palettes = fp.screen && r + (1 << bsl) <= geo.mi_rows && c + (1 << bsl) <= geo.mi_cols;
+    o.b = BlkInfo{};
+    o.b.bsl = (uint8_t)bsl;
+    o.b.mode = (uint8_t)mode;
+    o.b.uv_mode = DC_PRED;
+    memset(o.col, 0, kPalMax);
     o.col_u = o.col_v = 0;
-    const int kuv = fp.screen && chroma_palette && visible ? palette_colors_uv(su, sv, g.stride_c, cn, &o.col_u, &o.col_v) : 0;
-    if (kuv) {
-        uint8_t map[64];
-        int rate2 = palette_uv_rate2_head(o.col_u, o.col_v, kuv);
-        for (int i = 0; i < cn; i++)
-            for (int j = 0; j < cn; j++)
-                map[i * cn + j] = (uint8_t)palette_index_uv(o.col_u, o.col_v, kuv, su[(size_t)i * g.stride_c + j],
-                                                            sv[(size_t)i * g.stride_c + j]);
-        for (int i = 0; i < cn; i++)
-            for (int j = 0; j < cn; j++) rate2 += palette_rate2_px(map, cn, i, j, kuv);
-        if (tx_rd_cost(0, rate2, ac_q(fp.qidx)) < o.jc) {
-            o.jc = tx_rd_cost(0, rate2, ac_q(fp.qidx));
-            b.pal_n = (uint8_t)(b.pal_n | (kuv << 4));
-            memset(lu, 0, sizeof(int16_t) * cn * cn);
-            memset(lvv, 0, sizeof(int16_t) * cn * cn);
-            for (int i = 0; i < cn; i++) {
-                memcpy(&bu[i * cn], su + (size_t)i * g.stride_c, (size_t)cn);
-                memcpy(&bv[i * cn], sv + (size_t)i * g.stride_c, (size_t)cn);
-            }
-        }
+    // luma transform type: DCT_DCT or IDTX (screen content: sharp text codes as samples), by RD cost
+    intra_edges(fe.rec[0].data(), g.stride_y, x, y, n, au, al, geo.mi_cols * 4 - 1, geo.mi_rows * 4 - 1, w.e[0]);
+    intra_predict(w.e[0], mode, log2n, w.pred);
+    int16_t lid[256];
+    const long long jd = quant_block(w.src[0], g.stride_y, w.pred, log2n, fp.qidx, true, TX_DCT_DCT, o.lev);
+    const long long ji = quant_block(w.src[0], g.stride_y, w.pred, log2n, fp.qidx, true, TX_IDTX, lid);
+    o.b.tx_type = (int16_t)(ji < jd && any_nonzero(lid, n * n) ? TX_IDTX : TX_DCT_DCT);
+    if (o.b.tx_type == TX_IDTX) memcpy(o.lev, lid, sizeof(int16_t) * n * n);
+    o.jy = jd < ji ? jd : ji;
+    const int k = w.palettes ? try_luma_palette(w, o) : 0;
+    if (has_cluster(tools) && w.palettes && !k) try_luma_cluster(w, o);
+    bool nz = recon_block(o.lev, log2n, fp.qidx, true, o.b.tx_type, w.pred, o.rec, n);
+    // chroma: UV_DC_PRED first. Every other UV mode but UV_CFL_PRED implies an ADST-family chroma
+    // transform (Mode_To_Txfm, §7.13.3 compute_tx_type); this encoder's transforms are DCT_DCT.
+    o.jc = 0;
+    for (int p = 1; p < 3; p++) {
+        intra_edges(fe.rec[p].data(), g.stride_c, cx, cy, cn, au, al, geo.mi_cols * 2 - 1, geo.mi_rows * 2 - 1, w.e[p]);
+        intra_predict(w.e[p], DC_PRED, cl2, w.pred + plane_off(p));
+        o.jc += quant_block(w.src[p], g.stride_c, w.pred + plane_off(p), cl2, fp.qidx, true, TX_DCT_DCT, o.lev + plane_off(p));
     }
-    // chroma from luma (av1_cfl, av1_core.h): candidates kept a chroma level under UV_DC_PRED and have
-    // luma that varies; one alpha per plane, both planes coded again, against the chroma J standing
-    if (cfl && dc_kept) {
-        int ac[64], sum = 0;
-        bool flat = true;
-        for (int i = 0; i < cn; i++)
-            for (int j = 0; j < cn; j++) sum += ac[i * cn + j] = cfl_luma(o.rec, n, i, j);
-        const int avg = cfl_avg(sum, cl2);
-        for (int k = 0; k < cn * cn; k++) flat &= (ac[k] -= avg) == 0;
-        if (!flat) {
-            const uint8_t* sp[2] = {su, sv};
-            const int dc[2] = {intra_dc(eu, cl2), intra_dc(ev, cl2)};
-            int alpha[2];
-            long long sxx = 0;
-            for (int k = 0; k < cn * cn; k++) sxx += (long long)ac[k] * ac[k];
-            for (int p = 0; p < 2; p++) {
-                long long sxy = 0;
-                for (int i = 0; i < cn; i++)
-                    for (int j = 0; j < cn; j++) sxy += (long long)ac[i * cn + j] * ((int)sp[p][(size_t)i * g.stride_c + j] - dc[p]);
-                const int a0 = cfl_alpha0(sxx, sxy);
-                int best = 0x7fffffff;
-                alpha[p] = 0;
-                for (int q = 0; q < 3; q++) {
-                    const int a = cfl_cand(a0, sxy, q);
-                    int sse = 0;
-                    for (int i = 0; i < cn; i++)
-                        for (int j = 0; j < cn; j++) {
-                            const int e = (int)sp[p][(size_t)i * g.stride_c + j] - cfl_px(dc[p], a, ac[i * cn + j]);
-                            sse += e * e;
-                        }
-                    if (sse < best) {
-                        best = sse;
-                        alpha[p] = a;
-                    }
-                }
-            }
-            if (alpha[0] || alpha[1]) {
-                uint8_t pc[2][64];
-                int16_t lc[2][64];
-                long long j = tx_rd_cost(0, cfl_rate2(alpha[0], alpha[1]), ac_q(fp.qidx));
-                for (int p = 0; p < 2; p++) {
-                    for (int k = 0; k < cn * cn; k++) pc[p][k] = (uint8_t)cfl_px(dc[p], alpha[p], ac[k]);
-                    j += quant_block(sp[p], g.stride_c, pc[p], cl2, fp.qidx, true, TX_DCT_DCT, lc[p]);
-                }
-                if (j < o.jc) {
-                    o.jc = j;
-                    b.uv_mode = UV_CFL_PRED;
-                    b.pal_n &= 15;
-                    b.mv_row = (int16_t)alpha[0];
-                    b.mv_col = (int16_t)alpha[1];
-                    memcpy(bu, pc[0], (size_t)cn * cn);
-                    memcpy(bv, pc[1], (size_t)cn * cn);
-                    memcpy(lu, lc[0], sizeof(int16_t) * cn * cn);
-                    memcpy(lvv, lc[1], sizeof(int16_t) * cn * cn);
-                }
-            }
-        }
-    }
-    nz |= recon_block(lu, cl2, fp.qidx, true, TX_DCT_DCT, bu, o.rec + 256, cn);
-    nz |= recon_block(lvv, cl2, fp.qidx, true, TX_DCT_DCT, bv, o.rec + 320, cn);
-    b.flags = nz ? 0 : 2;
-    o.b = b;
+    const bool dc_kept = any_nonzero(o.lev + plane_off(1), cn * cn) || any_nonzero(o.lev + plane_off(2), cn * cn);
+    if (has_uv(tools) && w.palettes) try_chroma_palette(w, o);
+    if (has_cfl(tools) && dc_kept) try_cfl(w, o);   // dc_kept: before a palette cleared the levels
+    for (int p = 1; p < 3; p++)
+        nz |= recon_block(o.lev + plane_off(p), cl2, fp.qidx, true, TX_DCT_DCT, w.pred + plane_off(p), o.rec + plane_off(p), cn);
+    o.b.flags = nz ? 0 : 2;
 }
 
 // Makes an intra coding the block's: reconstruction, levels, level contexts, cells, palette cells.
@@ -534,16 +542,14 @@ void CpuAv1Encoder::intra_commit(int r, int c, int bsl, const IntraCoding& o) {
     const h264::Geometry& g = fe.g;
     const int n = 4 << bsl, cn = n >> 1, x = c * 4, y = r * 4, cx = x >> 1, cy = y >> 1;
     for (int i = 0; i < n; i++) memcpy(&fe.rec[0][(size_t)(y + i) * g.stride_y + x], o.rec + i * n, (size_t)n);
-    for (int i = 0; i < cn; i++) {
-        memcpy(&fe.rec[1][(size_t)(cy + i) * g.stride_c + cx], o.rec + 256 + i * cn, (size_t)cn);
-        memcpy(&fe.rec[2][(size_t)(cy + i) * g.stride_c + cx], o.rec + 320 + i * cn, (size_t)cn);
-    }
+    for (int p = 1; p < 3; p++)
+        for (int i = 0; i < cn; i++) memcpy(&fe.rec[p][(size_t)(cy + i) * g.stride_c + cx], o.rec + plane_off(p) + i * cn, (size_t)cn);
     int16_t* ly = unit_lev(r, c, bsl, 0);
     int16_t* lu = unit_lev(r, c, bsl, 1);
     int16_t* lvv = unit_lev(r, c, bsl, 2);
     memcpy(ly, o.lev, sizeof(int16_t) * n * n);
-    memcpy(lu, o.lev + 256, sizeof(int16_t) * cn * cn);
-    memcpy(lvv, o.lev + 320, sizeof(int16_t) * cn * cn);
+    memcpy(lu, o.lev + plane_off(1), sizeof(int16_t) * cn * cn);
+    memcpy(lvv, o.lev + plane_off(2), sizeof(int16_t) * cn * cn);
     if (pal_ny(o.b)) set_palette(r, c, bsl, o.col);
     if (pal_nuv(o.b)) set_palette_uv(r, c, bsl, o.col_u, o.col_v);
     set_cells(r, c, bsl, o.b);
@@ -827,19 +833,19 @@ std::vector<uint8_t> CpuAv1Encoder::code_tile(int t) {
     return out;
 }
 
-std::vector<uint8_t> CpuAv1Encoder::assemble(const std::vector<std::vector<uint8_t>>& tiles) {
+void write_temporal_unit(std::vector<uint8_t>& out, const Av1Geo& g, FrameParams& fp,
+                         const std::vector<std::vector<uint8_t>>& tiles, int level_idx, int full_range) {
     size_t maxsz = 1;
     for (size_t i = 0; i + 1 < tiles.size(); i++) maxsz = std::max(maxsz, tiles[i].size());
     fp.tile_size_bytes = maxsz <= 0x100 ? 1 : (maxsz <= 0x10000 ? 2 : (maxsz <= 0x1000000 ? 3 : 4));
-    std::vector<uint8_t> out;
     append_obu(out, 2, nullptr, 0);   // temporal delimiter
     if (fp.key) {
         BitWriter sh;
-        write_sequence_header(sh, geo.W, geo.H, level_idx, fe.cfg.full_range);
+        write_sequence_header(sh, g.W, g.H, level_idx, full_range);
         append_obu(out, 1, sh.buf.data(), sh.buf.size());
     }
     BitWriter fh;
-    write_frame_header(fh, geo, fp);
+    write_frame_header(fh, g, fp);
     std::vector<uint8_t> payload = fh.buf;
     const int nt = (int)tiles.size();
     if (nt > 1) payload.push_back(0);   // tile_start_and_end_present_flag = 0 + byte_alignment
@@ -851,6 +857,11 @@ std::vector<uint8_t> CpuAv1Encoder::assemble(const std::vector<std::vector<uint8
         payload.insert(payload.end(), tiles[i].begin(), tiles[i].end());
     }
     append_obu(out, 6, payload.data(), payload.size());   // OBU_FRAME
+}
+
+std::vector<uint8_t> CpuAv1Encoder::assemble(const std::vector<std::vector<uint8_t>>& tiles) {
+    std::vector<uint8_t> out;
+    write_temporal_unit(out, geo, fp, tiles, level_idx, fe.cfg.full_range);
     return out;
 }
 
@@ -875,7 +886,7 @@ void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, s
         for (int s = 0; s < ns; s++) fe.tasks[s].final_action = ACT_I;
     fe.ctl_.rate_control(fe.tasks.data(), fe.me.data());   // K10
     fp.key = key;
-    fp.screen = (key || intra_inter) && palette_on;
+    fp.screen = frame_screen(key, tools, palette_on);
     if (fe.ltr_cfg.slots) {   // the buffers the header names, from the map before this frame's commit
         const ltr::LtrAv1Bufs b = ltr::ltr_av1_frame_bufs(fe.ltr_cfg, fe.ltr_state[ns], fe.ltr_task.data(), ns);
         fp.refresh = b.refresh;
@@ -899,7 +910,7 @@ void CpuAv1Encoder::encode(const uint8_t* bgrx, int stride, uint16_t frame_id, s
             decide_key();
         } else {
             decide_inter();
-            if (intra_inter) decide_intra_inter();
+            if (has_intra_inter(tools)) decide_intra_inter();
             merge_static();
             decide_modes();
         }

@@ -41,6 +41,12 @@ inline bool palette_enabled() {
     const char* e = getenv("SK_AV1_PALETTE");
     return !(e && e[0] == '0');
 }
+// The session's tools word (av1_core.h Tools) from its configuration. A chroma palette and a
+// clustered palette act only where luma palettes do, so a session without palettes has neither.
+inline int session_tools(const h264::EncoderConfig& c, bool palette) {
+    return (c.av1_chroma_palette > 0 && palette ? kToolUv : 0) | (c.av1_cfl > 0 ? kToolCfl : 0) |
+           (c.av1_palette_cluster > 0 && palette ? kToolCluster : 0) | (c.av1_intra_inter > 0 ? kToolIntraInter : 0);
+}
 
 // MSB-first bit writer for headers.
 struct BitWriter {
@@ -66,6 +72,10 @@ void write_sequence_header(BitWriter& w, int W, int H, int level_idx, int full_r
 void write_frame_header(BitWriter& w, const Av1Geo& g, const FrameParams& fp);
 // OBU = header byte (type, has_size_field) + leb128 size + payload
 void append_obu(std::vector<uint8_t>& out, int type, const uint8_t* payload, size_t n);
+// The temporal unit of one frame appended to out: temporal delimiter, on key frames the sequence
+// header, and the frame OBU with the tiles' payloads; sets fp.tile_size_bytes from the tiles.
+void write_temporal_unit(std::vector<uint8_t>& out, const Av1Geo& g, FrameParams& fp,
+                         const std::vector<std::vector<uint8_t>>& tiles, int level_idx, int full_range);
 int choose_level_idx(int W, int H, float fps);
 int qidx_for_qp(int qp);
 // Open-loop intra mode of an n x n luma block (source edges, decoder availability).
@@ -119,10 +129,7 @@ class CpuAv1Encoder {
     std::vector<uint8_t> pal;        // c8 * r8 * 8: palette colours of each cell's block
     std::vector<uint8_t> pal_uv;     // c8 * r8 * 16: chroma palette of each cell's block, U at 0, V at 8 (av1_chroma_palette)
     bool palette_on = palette_enabled();
-    bool intra_inter = false;        // EncoderConfig::av1_intra_inter
-    bool chroma_palette = false;     // EncoderConfig::av1_chroma_palette (acts where palettes do: fp.screen)
-    bool cfl = false;                // EncoderConfig::av1_cfl (acts on every intra block)
-    bool palette_cluster = false;    // EncoderConfig::av1_palette_cluster (acts where palettes do: fp.screen)
+    int tools = 0;                   // the session's tools word (av1_core.h Tools, session_tools)
     std::vector<long long> jinter;   // c8 * r8: J of the inter coding of the block at that origin cell (inter_block)
     int lctx_w[3] = {0, 0, 0}, lctx_h[3] = {0, 0, 0};
     int level_idx = 8;
@@ -132,7 +139,7 @@ class CpuAv1Encoder {
     FrameView view() const;
 
    private:
-    // An intra coding of one block, not yet the block's: luma at 0, U at 256, V at 320 (raster per plane)
+    // An intra coding of one block, not yet the block's: plane p at plane_off(p) (raster per plane)
     struct IntraCoding {
         BlkInfo b;
         int16_t lev[384];
@@ -141,7 +148,14 @@ class CpuAv1Encoder {
         uint64_t col_u, col_v;   // chroma palette pairs (av1_core.h pal_byte), PaletteSizeUV in b
         long long jy, jc;   // tx_rd_cost of the luma coding kept and of both chroma planes
     };
+    struct IntraWork;
     void intra_code(int r, int c, int bsl, const TileRect& t, int mode, IntraCoding& o) const;
+    // the candidates of intra_code, each against the coding standing in `o` (the kernels'
+    // intra_rec_block runs the same chain under the same names)
+    int try_luma_palette(IntraWork& w, IntraCoding& o) const;
+    void try_luma_cluster(IntraWork& w, IntraCoding& o) const;
+    void try_chroma_palette(IntraWork& w, IntraCoding& o) const;
+    void try_cfl(IntraWork& w, IntraCoding& o) const;
     void intra_commit(int r, int c, int bsl, const IntraCoding& o);
     void intra_trial(int r, int c, int bsl, const TileRect& t);
     void intra_block(int r, int c, int bsl, const TileRect& t);

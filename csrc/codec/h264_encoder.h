@@ -80,6 +80,16 @@ inline int ltr_slots_of(const EncoderConfig& c) {
     return c.ltr_slots > 0 ? (c.ltr_slots < cap ? c.ltr_slots : cap) : 0;
 }
 
+// The four AV1 tool options from a session's API values (> 0: on), after c.codec is set: the other
+// codecs run with all of them off.
+inline void set_av1_tools(EncoderConfig& c, int intra_inter, int chroma_palette, int cfl, int palette_cluster) {
+    const bool av1 = c.codec == 2;
+    c.av1_intra_inter = av1 && intra_inter > 0 ? 1 : 0;
+    c.av1_chroma_palette = av1 && chroma_palette > 0 ? 1 : 0;
+    c.av1_cfl = av1 && cfl > 0 ? 1 : 0;
+    c.av1_palette_cluster = av1 && palette_cluster > 0 ? 1 : 0;
+}
+
 // HEVC cache expiry age in pictures (ltr.h ltr_expire): SK_HEVC_LTR_MAX_AGE=<n>, clipped to
 // 2..32768 (tests exercise expiry at small sizes); read once when an encoder is built.
 inline int ltr_max_age_env() {

@@ -69,22 +69,15 @@ struct Av1Args {
     BlkInfo* blk;             // [r8][c8]
     uint8_t* pal;             // [r8][c8][8] palette colours of each cell's block (key frames)
     int palette;              // palette coding of key frames enabled (av1_encoder.h palette_enabled)
-    int* pal_rate;            // [r8][c8] palette_rate2 of the block at that origin cell (key frames:
-                              // k_av1_intra_modes; its colour count rides in BlkInfo.pad1 until
-                              // k_av1_intra_rec decides; inter frames: k_av1_cand_modes, count in cand)
-    int chroma_palette;       // EncoderConfig::av1_chroma_palette (and palette): chroma palettes on the blocks above
+    int tools;                // the session's tools word (av1_core.h Tools; av1_encoder.h session_tools)
+    int* pal_rate;            // [r8][c8] palette_rate2 of the luma palette candidate of the block at that origin cell
+                              // (k_av1_intra_modes / k_av1_cand_modes; a clustered candidate's word carries
+                              // kPalClusterMark). The candidates' counts: av1_core.h cand_pack
     uint8_t* pal_uv;          // [r8][c8][16] chroma palette of each cell's block: U at 0, V at 8 (av1_core.h FrameView)
-    int* pal_rate_uv;         // [r8][c8] rate (half bits) of the chroma palette candidate of the block at that origin
-                              // cell; its pair count rides in the high nibble of BlkInfo.pad1 (key frames) or in
-                              // bits 20..23 of cand (inter frames)
-    int cfl;                  // EncoderConfig::av1_cfl: chroma from luma on intra blocks (k_av1_intra_rec, k_av1_inter_intra,
-                              // k_av1_tokens; the alphas ride in an intra cell's mv_row / mv_col, av1_core.h)
-    int palette_cluster;      // EncoderConfig::av1_palette_cluster (and palette): clustered luma palettes with a residual.
-                              // A clustered candidate is marked by bit 30 of its pal_rate word (kPalClusterMark)
-    int intra_inter;          // EncoderConfig::av1_intra_inter: intra blocks in inter frames; the three below only then
+    int* pal_rate_uv;         // [r8][c8] rate (half bits) of the chroma palette candidate of the block at that origin cell
+    // kToolIntraInter only:
     long long* jinter;        // [r8][c8] J of the inter coding of the block at that origin cell (k_av1_inter)
-    int* cand;                // [r8][c8] bit 0: the block is an intra candidate (its inter coding kept levels),
-                              // bits 8..15 its open-loop mode, bits 16..19 its palette colour count (k_av1_cand_modes)
+    int* cand;                // [r8][c8] the candidate word of the block at that origin cell (cand_pack; k_av1_cand_modes)
     int* tile_cand;           // [tiles] candidates of the tile (k_av1_setup clears, k_av1_inter counts)
     int16_t* lev;             // [units][kLevPerUnit]
     uint8_t* lctx[3];         // level contexts per plane (4x4 units), strides lctx_w

@@ -22,11 +22,14 @@
 //   k_av1_lf           in-loop deblocking (codec/av1_lf.h), one launch per plane and pass
 //   k_av1_cdef         CDEF (codec/av1_cdef.h), one wave per 8x8, from a copy of the deblocked picture
 //   k_av1_finish       padding rows of the reconstruction, slice actions for k_commit
-// av1_chroma_palette selects the <true> instantiations of k_av1_intra_modes / cand_modes / intra_rec /
-// inter_intra / tokens (chroma candidate, decision and syntax); <false> is the kernel without them.
+// The session's tools (Av1Args::tools; av1_core.h Tools) select the instantiation kTools of
+// k_av1_intra_rec / inter_intra / tokens (eight each) and, without the CfL bit, of k_av1_intra_modes /
+// cand_modes (four each): candidate, decision and syntax of a tool are compiled in only where the
+// session runs with it (by_tools, launch_code). kToolIntraInter is a run-time switch of launch_code.
 // Transforms: forward DCT as LDS matrix products (lanes = output coefficients),
 // inverse as the normative butterflies, lane = row / column of a transform block.
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "av1_gpu.h"
@@ -78,7 +81,13 @@ __device__ __forceinline__ void load_fdct(FdctLds& F) {
     }
 }
 
-// One block's working set: luma n x n at 0, U at 256, V at 320 (raster per plane).
+// One block's working set: plane p at plane_off(p) (raster per plane).
+// After code_block_wave the block's coding is L.lv (levels) and L.pred (reconstruction); L.a, L.b and
+// L.lv2 are dead. A candidate that codes a part of the block again (recode_*_wave: L.a, L.b and the
+// part's own L.lv / L.lv2) parks the coding standing where that does not reach:
+//   luma   (park_luma):   levels in L.b's chroma part (128 words = 256 levels), samples in L.lv2's
+//                         chroma part (128 levels = 256 bytes)
+//   chroma (park_chroma): levels in L.lv2's chroma part, samples in L.a's luma part (U at 0, V at 64)
 struct BlkLds {
     uint8_t src[384];
     uint8_t pred[384];
@@ -90,6 +99,27 @@ struct BlkLds {
     long long jchr;      // kJ = 2: the J of both chroma planes of an intra block (trial; chroma palette decision)
     IntraEdge e[3];      // intra edges of Y, U, V
 };
+constexpr int kOffU = plane_off(1), kOffV = plane_off(2);
+__device__ __forceinline__ void park_luma(BlkLds& L, int i) {
+    ((int16_t*)(L.b + kOffU))[i] = L.lv[i];
+    ((uint8_t*)(L.lv2 + kOffU))[i] = L.pred[i];
+}
+__device__ __forceinline__ void unpark_luma(BlkLds& L, int i) {
+    L.lv[i] = ((const int16_t*)(L.b + kOffU))[i];
+    L.pred[i] = ((const uint8_t*)(L.lv2 + kOffU))[i];
+}
+__device__ __forceinline__ void park_chroma(BlkLds& L, int i) {
+    L.lv2[kOffU + i] = L.lv[kOffU + i];
+    L.lv2[kOffV + i] = L.lv[kOffV + i];
+    L.a[i] = L.pred[kOffU + i];
+    L.a[64 + i] = L.pred[kOffV + i];
+}
+__device__ __forceinline__ void unpark_chroma(BlkLds& L, int i) {
+    L.lv[kOffU + i] = L.lv2[kOffU + i];
+    L.lv[kOffV + i] = L.lv2[kOffV + i];
+    L.pred[kOffU + i] = (uint8_t)L.a[i];
+    L.pred[kOffV + i] = (uint8_t)L.a[64 + i];
+}
 // Tile of a unit position (mi r, c).
 __device__ __forceinline__ TileRect tile_of(const Av1Geo& g, int r, int c) {
     const int tc = (c >> 4) / g.tile_w_sb, tr = (r >> 4) / g.tile_h_sb;
@@ -263,8 +293,7 @@ __device__ __forceinline__ void inv_cols_lane(BlkLds& L, int ln, int o, int j, b
 // luma n = 1 << log2n, chroma n / 2. The transform type is DCT_DCT or IDTX by RD cost
 // (the CPU encoder's quant_block rule: inter blocks over the three planes, intra blocks
 // luma only, chroma DCT_DCT). Writes levels to gl (3 planes), the reconstruction into
-// L.pred, and returns the per-plane level summaries (cul | dc << 6) packed as bytes
-// 0..2, bit 24 = any nonzero, bit 25 = IDTX.
+// L.pred, and returns the block's level summary (av1_core.h summ_pack).
 // kJ (av1_intra_inter): 1 = an inter block that leaves the three-plane J its RD skip compared in
 // L.jreg; 2 = an intra block on trial, or one that may take a chroma palette: the chroma J into
 // L.jchr too, and no level goes to gy / gu / gv (the final levels stay in L.lv for the caller to
@@ -275,11 +304,9 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     const int l = lane();
     const int n = 1 << log2n, nn = n * n, cn = n >> 1, cnn = cn * cn;
     const int qd = dc_q(qidx), qa = ac_q(qidx);
-    // plane p element i: luma [0, nn), U [256, 256 + cnn), V [320, 320 + cnn)
-    auto base = [&](int p) { return p == 0 ? 0 : (p == 1 ? 256 : 320); };
     int e2 = 0;   // the residual's SSE: J of coding nothing (inter RD skip)
     for (int p = 0; p < 3; p++) {
-        const int m = p ? cnn : nn, o = base(p);
+        const int m = p ? cnn : nn, o = plane_off(p);
         for (int i = l; i < m; i += 64) {
             const int e = (int)L.src[o + i] - (int)L.pred[o + i];
             L.a[o + i] = e;
@@ -288,7 +315,7 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     }
     const long long jz = 256ll * wsum(e2);
     wsync();
-    for (int p = 0; p < 3; p++) fwd_cols_plane(L, F, p ? log2n - 1 : log2n, base(p));
+    for (int p = 0; p < 3; p++) fwd_cols_plane(L, F, p ? log2n - 1 : log2n, plane_off(p));
     wsync();
     // forward stage 2 (rows) + quantisation, DCT levels to L.lv and IDTX levels (8 x the
     // residual, still in L.a) to L.lv2, with both squared coefficient errors per plane
@@ -296,7 +323,7 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
     long long jd = 0, ji = 0;
     const int np = intra ? 1 : 3;   // planes in the decision
     for (int p = 0; p < 3; p++) {
-        const int ln = p ? log2n - 1 : log2n, o = base(p);
+        const int ln = p ? log2n - 1 : log2n, o = plane_off(p);
         long long ed = 0, ei = 0;
         fwd_rows_quant_plane(L, F, ln, o, qd, qa, intra, p < np, ed, ei);
         const long long dp = wsum64(ed), ip = wsum64(ei);
@@ -324,36 +351,32 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
         } else {
             // IDTX only where the DCT codes something and the luma keeps levels after trimming
             bool dct_codes = false;
-            for (int p = 0; p < 3; p++) dct_codes |= trim_cut_wave(L.lv + base(p), p ? log2n - 1 : log2n, false) >= 0;
+            for (int p = 0; p < 3; p++) dct_codes |= trim_cut_wave(L.lv + plane_off(p), p ? log2n - 1 : log2n, false) >= 0;
             idtx = dct_codes && ji < jd && trim_cut_wave(L.lv2, log2n, false) >= 0;
         }
     }
     wsync();
     if (idtx)
         for (int p = 0; p < np; p++) {
-            const int m = p ? cnn : nn, o = base(p);
+            const int m = p ? cnn : nn, o = plane_off(p);
             for (int i = l; i < m; i += 64) L.lv[o + i] = L.lv2[o + i];
         }
     // inter RD skip (av1_cpu.cpp inter_block): nothing coded when the levels do not pay
     if (kJ == 1 && l == 0) L.jreg = idtx ? ji : jd;
     if (!intra && jz <= (idtx ? ji : jd))
         for (int p = 0; p < 3; p++) {
-            const int m = p ? cnn : nn, o = base(p);
+            const int m = p ? cnn : nn, o = plane_off(p);
             for (int i = l; i < m; i += 64) L.lv[o + i] = 0;
         }
     wsync();
     // inter blocks: tail trimming of the chosen levels
     if (!intra)
-        for (int p = 0; p < 3; p++) trim_cut_wave(L.lv + base(p), p ? log2n - 1 : log2n, true);
+        for (int p = 0; p < 3; p++) trim_cut_wave(L.lv + plane_off(p), p ? log2n - 1 : log2n, true);
     wsync();
     // dequantisation, level summaries
-    int nzm = 0;
-    uint32_t cul = 0;
-    for (int p = 0; p < 3; p++) {
-        const uint32_t summ = dequant_plane<kJ != 2>(L, p ? log2n - 1 : log2n, base(p), qd, qa, p == 0 ? gy : (p == 1 ? gu : gv));
-        if (summ) nzm |= 1 << p;   // a plane with a level has a nonzero sum
-        cul |= summ << (8 * p);
-    }
+    uint32_t cul = 0;   // a plane with a level has a nonzero summary
+    for (int p = 0; p < 3; p++)
+        cul |= dequant_plane<kJ != 2>(L, p ? log2n - 1 : log2n, plane_off(p), qd, qa, p == 0 ? gy : (p == 1 ? gu : gv)) << (8 * p);
     wsync();
     // inverse: rows (lane = row of one plane's block), then columns
     const int rows_y = n, rows_c = cn;
@@ -361,7 +384,7 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
         const int p = l < rows_y ? 0 : (l < rows_y + rows_c ? 1 : (l < rows_y + 2 * rows_c ? 2 : 3));
         if (p < 3) {
             const int i = p == 0 ? l : (p == 1 ? l - rows_y : l - rows_y - rows_c);
-            inv_rows_lane(L, p ? log2n - 1 : log2n, base(p), i, idtx && p < np);
+            inv_rows_lane(L, p ? log2n - 1 : log2n, plane_off(p), i, idtx && p < np);
         }
     }
     wsync();
@@ -369,11 +392,11 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
         const int p = l < rows_y ? 0 : (l < rows_y + rows_c ? 1 : (l < rows_y + 2 * rows_c ? 2 : 3));
         if (p < 3) {
             const int j = p == 0 ? l : (p == 1 ? l - rows_y : l - rows_y - rows_c);
-            inv_cols_lane(L, p ? log2n - 1 : log2n, base(p), j, idtx && p < np);
+            inv_cols_lane(L, p ? log2n - 1 : log2n, plane_off(p), j, idtx && p < np);
         }
     }
     wsync();
-    return cul | (nzm ? (1u << 24) : 0u) | (idtx && nzm ? (1u << 25) : 0u);   // no levels: DCT_DCT
+    return summ_pack(cul, idtx);
 }
 
 // av1_cfl: both chroma planes of an intra block coded again, DCT_DCT, from the prediction in
@@ -383,13 +406,14 @@ __device__ uint32_t code_block_wave(BlkLds& L, const FdctLds& F, int log2n, int 
 __device__ long long recode_chroma_wave(BlkLds& L, const FdctLds& F, int log2n, int qidx) {
     const int l = lane(), ln = log2n - 1, cnn = 1 << (2 * ln);
     const int qd = dc_q(qidx), qa = ac_q(qidx);
-    for (int o = 256; o <= 320; o += 64)
-        for (int i = l; i < cnn; i += 64) L.a[o + i] = (int)L.src[o + i] - (int)L.pred[o + i];
+    for (int p = 1; p < 3; p++)
+        for (int i = l; i < cnn; i += 64) L.a[plane_off(p) + i] = (int)L.src[plane_off(p) + i] - (int)L.pred[plane_off(p) + i];
     wsync();
-    for (int o = 256; o <= 320; o += 64) fwd_cols_plane(L, F, ln, o);
+    for (int p = 1; p < 3; p++) fwd_cols_plane(L, F, ln, plane_off(p));
     wsync();
     long long j = 0;
-    for (int o = 256; o <= 320; o += 64) {
+    for (int p = 1; p < 3; p++) {
+        const int o = plane_off(p);
         long long ed = 0, ei = 0;
         fwd_rows_quant_plane(L, F, ln, o, qd, qa, true, false, ed, ei);
         const long long dp = wsum64(ed);
@@ -438,9 +462,9 @@ __device__ uint32_t recon_chroma_wave(BlkLds& L, int log2n, int qidx) {
     const int l = lane(), ln = log2n - 1, cn = 1 << ln;
     const int qd = dc_q(qidx), qa = ac_q(qidx);
     uint32_t cul = 0;
-    for (int p = 1; p < 3; p++) cul |= dequant_plane<false>(L, ln, p == 1 ? 256 : 320, qd, qa, nullptr) << (8 * p);
+    for (int p = 1; p < 3; p++) cul |= dequant_plane<false>(L, ln, plane_off(p), qd, qa, nullptr) << (8 * p);
     wsync();
-    const int o = l < cn ? 256 : 320, k = l < cn ? l : l - cn;   // lane = row, then column, of one plane
+    const int o = l < cn ? kOffU : kOffV, k = l < cn ? l : l - cn;   // lane = row, then column, of one plane
     if (l < 2 * cn) inv_rows_lane(L, ln, o, k, false);
     wsync();
     if (l < 2 * cn) inv_cols_lane(L, ln, o, k, false);
@@ -455,7 +479,7 @@ __device__ __forceinline__ void load_src_blk(BlkLds& L, const FrameArgs& f, int 
     for (int i = l; i < 2 * cn * cn; i += 64) {
         const int p = i / (cn * cn), j = i % (cn * cn);
         const uint8_t* P = p ? f.src.v : f.src.u;
-        L.src[(p ? 320 : 256) + j] = P[(size_t)((y >> 1) + j / cn) * f.stride_c + (x >> 1) + j % cn];
+        L.src[(p ? kOffV : kOffU) + j] = P[(size_t)((y >> 1) + j / cn) * f.stride_c + (x >> 1) + j % cn];
     }
 }
 __device__ __forceinline__ void store_rec_blk(const BlkLds& L, const FrameArgs& f, int x, int y, int n) {
@@ -464,7 +488,7 @@ __device__ __forceinline__ void store_rec_blk(const BlkLds& L, const FrameArgs& 
     for (int i = l; i < 2 * cn * cn; i += 64) {
         const int p = i / (cn * cn), j = i % (cn * cn);
         uint8_t* P = p ? f.rec.v : f.rec.u;
-        P[(size_t)((y >> 1) + j / cn) * f.stride_c + (x >> 1) + j % cn] = L.pred[(p ? 320 : 256) + j];
+        P[(size_t)((y >> 1) + j / cn) * f.stride_c + (x >> 1) + j % cn] = L.pred[(p ? kOffV : kOffU) + j];
     }
 }
 
@@ -526,9 +550,9 @@ __device__ __forceinline__ void set_lctx(const Av1Args& A, int p, int x4, int y4
 }
 __device__ __forceinline__ int16_t* lev_ptr(const Av1Args& A, int r, int c, int bsl, int p) {
     int16_t* u = A.lev + ((size_t)(r >> 2) * A.f.mb_w + (c >> 2)) * kLevPerUnit;
-    if (bsl >= 2) return u + (p == 0 ? 0 : (p == 1 ? 256 : 320));
+    if (bsl >= 2) return u + plane_off(p);
     const int k = ((r >> 1) & 1) * 2 + ((c >> 1) & 1);
-    return u + (p == 0 ? 64 * k : (p == 1 ? 256 + 16 * k : 320 + 16 * k));
+    return u + plane_off(p) + (p == 0 ? 64 : 16) * k;
 }
 
 // Blocks of a unit: one 16x16 (returns -1), or the inside 8x8s in Z order at frame edges
@@ -571,7 +595,7 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
             f.tasks[s].final_action = ACT_I;
             f.tasks_host[s].final_action = ACT_I;
         }
-    if (A.intra_inter)   // candidates per tile, counted by k_av1_inter
+    if (has_intra_inter(A.tools))   // candidates per tile, counted by k_av1_inter
         for (int t = threadIdx.x; t < A.geo.tile_cols * A.geo.tile_rows; t += 256) A.tile_cand[t] = 0;
     if (threadIdx.x == 0) {
         // K10: the frame's fractional QP under CRF / CBR (slices dither on H.264 / HEVC)
@@ -595,21 +619,40 @@ __global__ __launch_bounds__(256) void k_av1_setup(Av1Args A) {
     }
 }
 
-// Open-loop intra mode of the block at (r, c) from the source edges, by one wave (E, seen, map, col:
-// the wave's LDS). Palette candidate (source only, so decided here in parallel rather than in the
-// reconstruction wavefront): the block's distinct luma values, its colours into the palette
-// cells, palette_rate2 into pal_rate for the RD comparison of the reconstruction. *pal_k: the
-// colour count of the candidate (0: none) in the low nibble; with av1_chroma_palette the chroma
-// candidate's pair count in the high nibble (pairs into the pal_uv cells, rate into pal_rate_uv).
-// kUv: the session runs with av1_chroma_palette (its own kernels: without it they are what they were).
-// kCl: the session runs with av1_palette_cluster. A block with more than kPalMax values that the open-loop
-// rule admits (av1_core.h palette_cluster, the same integers here) gets clustered colours: the histogram in
-// hist (256 words of LDS), one distinct value per lane as a group (sum, count), the colour count by wave
-// minima, each merge step one wave minimum over the adjacent pairs' costs; no per-lane arrays.
-// Its pal_rate word carries kPalClusterMark.
-template <bool kUv, bool kCl>
-__device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdge& E, uint32_t* seen, uint8_t* map,
-                               uint8_t* col, uint32_t* hist, int* pal_k) {
+// The open-loop decisions of one block by one wave, from the source alone, so decided here in parallel
+// rather than in the reconstruction wavefront: the intra mode and the palette candidates. A candidate's
+// colours go to the palette cells of its block, its rate (half bits) to pal_rate / pal_rate_uv for the
+// RD comparison of the reconstruction, its count into the candidate word (av1_core.h cand_pack).
+// Candidates exist only for fully visible blocks. ModeLds: the wave's scratch.
+struct ModeLds {
+    IntraEdge& E;
+    uint32_t* seen;   // [8] the bit set of the block's luma values
+    uint8_t* map;     // [256] an index map
+    uint8_t* col;     // [8] the exact palette's colours
+    uint32_t* hist;   // [256] the luma histogram (sessions with kToolCluster)
+};
+__device__ __forceinline__ int src_luma(const FrameArgs& f, int r, int c, int n, int i) {
+    return f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n];
+}
+// A candidate's colours into the cells of its block, `per` bytes a cell: 8 (luma, from lo) or 16
+// (chroma: U from lo at 0, V from hi at 8).
+__device__ __forceinline__ void store_palette_cells(uint8_t* cells, int per, const Av1Geo& g, int r, int c, int bsl,
+                                                    uint64_t lo, uint64_t hi) {
+    const int n8 = (1 << bsl) >> 1;
+    for (int i = lane(); i < n8 * n8 * per; i += 64) {
+        const int cell = i / per, q = i % per, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
+        cells[((size_t)ry * g.c8 + cx) * per + q] = (uint8_t)pal_byte(q & 8 ? hi : lo, q & 7);
+    }
+}
+// The rate of the index map in S.map (pitch n, m = n * n samples) after `head`, by the whole wave.
+__device__ __forceinline__ int map_rate2_wave(const uint8_t* map, int n, int m, int k, int head) {
+    int r2 = 0;
+    for (int i = lane(); i < m; i += 64) r2 += palette_rate2_px(map, n, i / n, i % n, k);
+    return wsum(r2) + head;
+}
+
+// Intra mode by SAD against the predictions from the source edges (av1_cpu.cpp intra_mode_decision).
+__device__ __forceinline__ int sad_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdge& E) {
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
     const int l = lane(), log2n = bsl + 2, n = 1 << log2n;
@@ -624,7 +667,7 @@ __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdg
         int sad = 0;
         for (int i = l; i < n * n; i += 64) {
             const int pr = cand[m] == DC_PRED ? dc : intra_pred_px(E, cand[m], log2n, i / n, i % n);
-            sad += sk_abs((int)f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n] - pr);
+            sad += sk_abs(src_luma(f, r, c, n, i) - pr);
         }
         sad = wsum(sad);
         const int cost = sad + (cand[m] == DC_PRED ? 0 : n * 2);
@@ -633,217 +676,213 @@ __device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, IntraEdg
             best = cand[m];
         }
     }
-    *pal_k = 0;
-    if (A.palette && r + (1 << bsl) <= g.mi_rows && c + (1 << bsl) <= g.mi_cols) {
-        if (l < 8) seen[l] = 0u;
-        wsync();
-        for (int i = l; i < n * n; i += 64) {
-            const int v = f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n];
-            atomicOr(&seen[v >> 5], 1u << (v & 31));
-        }
-        wsync();
-        const int k = wsum(l < 8 ? __builtin_popcount(seen[l]) : 0);
-        if (k >= 2 && k <= kPalMax) {
-            if (l == 0) {
-                int q = 0;
-                for (int v = 0; v < 256; v++)
-                    if ((seen[v >> 5] >> (v & 31)) & 1) col[q++] = (uint8_t)v;
-                for (; q < 8; q++) col[q] = 0;
-            }
-            wsync();
-            for (int i = l; i < n * n; i += 64)
-                map[i] = (uint8_t)palette_index(col, k, f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]);
-            wsync();
-            int r2 = 0;
-            for (int i = l; i < n * n; i += 64) r2 += palette_rate2_px(map, n, i / n, i % n, k);
-            r2 = wsum(r2) + palette_rate2_head(k);
-            const int n8 = (1 << bsl) >> 1;
-            for (int i = l; i < n8 * n8 * 8; i += 64) {
-                const int cell = i >> 3, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
-                A.pal[((size_t)ry * g.c8 + cx) * 8 + (i & 7)] = col[i & 7];
-            }
-            if (l == 0) A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2;
-            *pal_k = k;
-        } else if (kCl && k > kPalMax && k <= kPalClusterValues && palette_cluster_tol(A.frame[1]) >= 1) {
-            for (int i = l; i < 256; i += 64) hist[i] = 0u;
-            wsync();
-            for (int i = l; i < n * n; i += 64)
-                atomicAdd(&hist[f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]], 1u);
-            wsync();
-            // lane i < k (the count of distinct values): the i-th value in ascending order, as a group
-            int val = 256, gs = 0, gn = 1;
-            {
-                int i = l;
-                for (int w = 0; w < 8; w++) {
-                    uint32_t bits = seen[w];
-                    const int cnt = __builtin_popcount(bits);
-                    if (i >= 0 && i < cnt) {
-                        for (; i > 0; i--) bits &= bits - 1u;
-                        val = 32 * w + __builtin_ctz(bits);
-                    }
-                    i -= cnt;   // negative once the lane has its value
-                }
-            }
-            if (l < k) {
-                gn = (int)hist[val];
-                gs = val * gn;
-            }
-            const int above = __shfl_down(val, 1);   // every lane takes part
-            const bool ramp = palette_has_ramp(__ballot(l + 1 < k && above - val <= kPalClusterRampGap));
-            int kc = 0;   // the fewest intervals of width 2 tol over the values, at most kPalMax (wave-uniform)
-            for (int hi = ramp ? 256 : -1, tol = palette_cluster_tol(A.frame[1]); kc < kPalMax; kc++) {
-                const int lo = __builtin_amdgcn_readfirstlane(wmin(val > hi ? val : 256));
-                if (lo == 256) break;
-                hi = lo + 2 * tol;
-            }
-            if (kc >= 2) {
-                for (int cur = k; cur > kc; cur--) {   // the cheapest adjacent pair merges; the groups above move down a lane
-                    const int s2 = __shfl_down(gs, 1), n2 = __shfl_down(gn, 1);
-                    const int key = l + 1 < cur ? (palette_merge_cost(gs, gn, s2, n2) << 6) | l : 0x7fffffff;
-                    const int bi = __builtin_amdgcn_readfirstlane(wmin(key)) & 63;
-                    if (l == bi) {
-                        gs += s2;
-                        gn += n2;
-                    } else if (l > bi && l + 1 < cur) {
-                        gs = s2;
-                        gn = n2;
-                    }
-                }
-                const int mean = palette_cluster_mean(gs, gn);
-                uint64_t C = 0;
-                for (int q = 0; q < kc; q++) C |= (uint64_t)__shfl(mean, q) << (8 * q);
-                for (int i = l; i < n * n; i += 64)
-                    map[i] = (uint8_t)palette_nearest(C, kc, f.src.y[(size_t)(r * 4 + i / n) * f.stride_y + c * 4 + i % n]);
-                wsync();
-                int r2 = 0;
-                for (int i = l; i < n * n; i += 64) r2 += palette_rate2_px(map, n, i / n, i % n, kc);
-                r2 = wsum(r2) + palette_rate2_head(kc);
-                const int n8 = (1 << bsl) >> 1;
-                for (int i = l; i < n8 * n8 * 8; i += 64) {
-                    const int cell = i >> 3, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
-                    A.pal[((size_t)ry * g.c8 + cx) * 8 + (i & 7)] = (uint8_t)pal_byte(C, i & 7);
-                }
-                if (l == 0) A.pal_rate[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2 | kPalClusterMark;
-                *pal_k = kc;
-            }
-        }
-        wsync();
-    }
-    // Chroma palette candidate (av1_core.h palette_colors_uv): one chroma sample per lane (64 of a
-    // 16x16 block, 16 of an 8x8), its pair packed as U << 8 | V. The distinct pairs come out in
-    // (U, V) order by repeated wave minima over the pairs above the last one found: at most nine
-    // rounds, each lane learns its pair's index on the way, and the pairs stay in two packed words.
-    if (kUv && r + (1 << bsl) <= g.mi_rows && c + (1 << bsl) <= g.mi_cols) {
-        const int cn = n >> 1, m = cn * cn;
-        int key = 0x10000;
-        if (l < m) {
-            const size_t o = (size_t)(r * 2 + l / cn) * f.stride_c + c * 2 + l % cn;
-            key = ((int)f.src.u[o] << 8) | (int)f.src.v[o];
-        }
-        uint64_t U = 0, V = 0;
-        int k = 0, cur = -1, idx = 0;
-        for (int q = 0; q <= kPalMax; q++) {
-            const int mn = __builtin_amdgcn_readfirstlane(wmin(key > cur ? key : 0x10000));   // wave-uniform: scalar
-            if (mn == 0x10000) break;
-            k = q + 1;
-            if (q == kPalMax) break;   // a ninth pair: no candidate
-            if (key == mn) idx = q;
-            U |= (uint64_t)(mn >> 8) << (8 * q);
-            V |= (uint64_t)(mn & 255) << (8 * q);
-            cur = mn;
-        }
-        if (k >= 2 && k <= kPalMax) {
-            if (l < m) map[l] = (uint8_t)idx;
-            wsync();
-            int r2 = l < m ? palette_rate2_px(map, cn, l / cn, l % cn, k) : 0;
-            r2 = wsum(r2) + palette_uv_rate2_head(U, V, k);
-            const int n8 = (1 << bsl) >> 1;
-            for (int i = l; i < n8 * n8 * 16; i += 64) {
-                const int cell = i >> 4, ry = (r >> 1) + cell / n8, cx = (c >> 1) + cell % n8;
-                A.pal_uv[((size_t)ry * g.c8 + cx) * 16 + (i & 15)] = (uint8_t)pal_byte(i & 8 ? V : U, i & 7);
-            }
-            if (l == 0) A.pal_rate_uv[(size_t)(r >> 1) * g.c8 + (c >> 1)] = r2;
-            *pal_k |= k << 4;
-        }
-        wsync();
-    }
     return best;
 }
 
-// Key frames: intra mode per block from the source edges (one wave per unit).
-template <bool kUv, bool kCl>
-__global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
-    if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
-    __shared__ IntraEdge E[4];
-    __shared__ uint32_t pal_seen[4][8];
-    __shared__ uint8_t pal_map[4][256], pal_col[4][8];
-    __shared__ uint32_t pal_hist[4][kCl ? 256 : 1];   // av1_palette_cluster: the luma histogram of the wave's block
-    if (!A.frame[0]) return;
+// Exact luma palette: the block's distinct values where there are 2..kPalMax of them. Returns the
+// colour count (0: no candidate) and in *values the count of distinct values, their bit set in S.seen.
+__device__ __forceinline__ int luma_palette_cand_wave(const Av1Args& A, int r, int c, int bsl, const ModeLds& S, int* values) {
     const FrameArgs& f = A.f;
-    const Av1Geo& g = A.geo;
-    const int w = threadIdx.x >> 6;
-    const int u = blockIdx.x * 4 + w;
-    if (u >= f.mb_w * f.mb_h) return;
-    const int ux = u % f.mb_w, uy = u / f.mb_w;
-    int nb = unit_blocks(g, uy, ux);
-    const int bsl = nb < 0 ? 2 : 1;
-    if (nb < 0) nb = 1;
-    for (int k = 0; k < nb; k++) {
-        int r, c, pal_k;
-        unit_block(g, uy, ux, k, r, c);
-        BlkInfo b{};
-        b.bsl = (uint8_t)bsl;
-        b.mode = (uint8_t)intra_mode_wave<kUv, kCl>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], pal_hist[w], &pal_k);
-        b.uv_mode = DC_PRED;
-        b.pad1 = (uint8_t)pal_k;   // the candidates' colour counts (luma | chroma << 4) ride in the cell until k_av1_intra_rec decides
-        set_cells(A, r, c, bsl, b);
-        wsync();
+    const int l = lane(), n = 4 << bsl;
+    if (l < 8) S.seen[l] = 0u;
+    wsync();
+    for (int i = l; i < n * n; i += 64) {
+        const int v = src_luma(f, r, c, n, i);
+        atomicOr(&S.seen[v >> 5], 1u << (v & 31));
     }
+    wsync();
+    const int k = wsum(l < 8 ? __builtin_popcount(S.seen[l]) : 0);
+    *values = k;
+    if (k < 2 || k > kPalMax) return 0;
+    if (l == 0) {
+        int q = 0;
+        for (int v = 0; v < 256; v++)
+            if ((S.seen[v >> 5] >> (v & 31)) & 1) S.col[q++] = (uint8_t)v;
+        for (; q < 8; q++) S.col[q] = 0;
+    }
+    wsync();
+    for (int i = l; i < n * n; i += 64) S.map[i] = (uint8_t)palette_index(S.col, k, src_luma(f, r, c, n, i));
+    wsync();
+    const int r2 = map_rate2_wave(S.map, n, n * n, k, palette_rate2_head(k));
+    store_palette_cells(A.pal, 8, A.geo, r, c, bsl, pal_load8(S.col), 0);
+    if (l == 0) A.pal_rate[(size_t)(r >> 1) * A.geo.c8 + (c >> 1)] = r2;
+    return k;
 }
 
-// Inter frames with av1_intra_inter: the same decision for every block whose inter coding kept
-// levels (k_av1_inter's cells: inter and not skipped), one wave per unit. The cells stay the inter
-// coding's, so the mode and the colour count travel in A.cand: bit 0 candidate, bits 8..15 the
-// mode, bits 16..19 the palette candidate's colour count, bits 20..23 the chroma palette candidate's.
-template <bool kUv, bool kCl>
-__global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
+// Clustered luma palette (kToolCluster) of a block with k > kPalMax distinct values (S.seen) that the
+// open-loop rule admits (av1_core.h palette_cluster, the same integers here): the histogram in S.hist,
+// one distinct value per lane as a group (sum, count), the colour count by wave minima, each merge step
+// one wave minimum over the adjacent pairs' costs; no per-lane arrays. Returns the colour count (0: no
+// candidate); the pal_rate word carries kPalClusterMark.
+__device__ __forceinline__ int luma_cluster_cand_wave(const Av1Args& A, int r, int c, int bsl, const ModeLds& S, int k) {
+    const FrameArgs& f = A.f;
+    const int l = lane(), n = 4 << bsl, tol = palette_cluster_tol(A.frame[1]);
+    if (k > kPalClusterValues || tol < 1) return 0;
+    for (int i = l; i < 256; i += 64) S.hist[i] = 0u;
+    wsync();
+    for (int i = l; i < n * n; i += 64) atomicAdd(&S.hist[src_luma(f, r, c, n, i)], 1u);
+    wsync();
+    // lane i < k: the i-th value in ascending order, as a group
+    int val = 256, gs = 0, gn = 1;
+    {
+        int i = l;
+        for (int w = 0; w < 8; w++) {
+            uint32_t bits = S.seen[w];
+            const int cnt = __builtin_popcount(bits);
+            if (i >= 0 && i < cnt) {
+                for (; i > 0; i--) bits &= bits - 1u;
+                val = 32 * w + __builtin_ctz(bits);
+            }
+            i -= cnt;   // negative once the lane has its value
+        }
+    }
+    if (l < k) {
+        gn = (int)S.hist[val];
+        gs = val * gn;
+    }
+    const int above = __shfl_down(val, 1);   // every lane takes part
+    const bool ramp = palette_has_ramp(__ballot(l + 1 < k && above - val <= kPalClusterRampGap));
+    int kc = 0;   // the fewest intervals of width 2 tol over the values, at most kPalMax (wave-uniform)
+    for (int hi = ramp ? 256 : -1; kc < kPalMax; kc++) {
+        const int lo = __builtin_amdgcn_readfirstlane(wmin(val > hi ? val : 256));
+        if (lo == 256) break;
+        hi = lo + 2 * tol;
+    }
+    if (kc < 2) return 0;
+    for (int cur = k; cur > kc; cur--) {   // the cheapest adjacent pair merges; the groups above move down a lane
+        const int s2 = __shfl_down(gs, 1), n2 = __shfl_down(gn, 1);
+        const int key = l + 1 < cur ? (palette_merge_cost(gs, gn, s2, n2) << 6) | l : 0x7fffffff;
+        const int bi = __builtin_amdgcn_readfirstlane(wmin(key)) & 63;
+        if (l == bi) {
+            gs += s2;
+            gn += n2;
+        } else if (l > bi && l + 1 < cur) {
+            gs = s2;
+            gn = n2;
+        }
+    }
+    const int mean = palette_cluster_mean(gs, gn);
+    uint64_t C = 0;
+    for (int q = 0; q < kc; q++) C |= (uint64_t)__shfl(mean, q) << (8 * q);
+    for (int i = l; i < n * n; i += 64) S.map[i] = (uint8_t)palette_nearest(C, kc, src_luma(f, r, c, n, i));
+    wsync();
+    const int r2 = map_rate2_wave(S.map, n, n * n, kc, palette_rate2_head(kc));
+    store_palette_cells(A.pal, 8, A.geo, r, c, bsl, C, 0);
+    if (l == 0) A.pal_rate[(size_t)(r >> 1) * A.geo.c8 + (c >> 1)] = r2 | kPalClusterMark;
+    return kc;
+}
+
+// Chroma palette (kToolUv; av1_core.h palette_colors_uv): one chroma sample per lane (64 of a 16x16
+// block, 16 of an 8x8), its pair packed as U << 8 | V. The distinct pairs come out in (U, V) order by
+// repeated wave minima over the pairs above the last one found: at most nine rounds, each lane learns
+// its pair's index on the way, and the pairs stay in two packed words. Returns the pair count (0: none).
+__device__ __forceinline__ int chroma_palette_cand_wave(const Av1Args& A, int r, int c, int bsl, uint8_t* map) {
+    const FrameArgs& f = A.f;
+    const int l = lane(), cn = 2 << bsl, m = cn * cn;
+    int key = 0x10000;
+    if (l < m) {
+        const size_t o = (size_t)(r * 2 + l / cn) * f.stride_c + c * 2 + l % cn;
+        key = ((int)f.src.u[o] << 8) | (int)f.src.v[o];
+    }
+    uint64_t U = 0, V = 0;
+    int k = 0, cur = -1, idx = 0;
+    for (int q = 0; q <= kPalMax; q++) {
+        const int mn = __builtin_amdgcn_readfirstlane(wmin(key > cur ? key : 0x10000));   // wave-uniform: scalar
+        if (mn == 0x10000) break;
+        k = q + 1;
+        if (q == kPalMax) break;   // a ninth pair: no candidate
+        if (key == mn) idx = q;
+        U |= (uint64_t)(mn >> 8) << (8 * q);
+        V |= (uint64_t)(mn & 255) << (8 * q);
+        cur = mn;
+    }
+    if (k < 2 || k > kPalMax) return 0;
+    if (l < m) map[l] = (uint8_t)idx;
+    wsync();
+    const int r2 = map_rate2_wave(map, cn, m, k, palette_uv_rate2_head(U, V, k));
+    store_palette_cells(A.pal_uv, 16, A.geo, r, c, bsl, U, V);
+    if (l == 0) A.pal_rate_uv[(size_t)(r >> 1) * A.geo.c8 + (c >> 1)] = r2;
+    return k;
+}
+
+// The candidate word of the block at (r, c). kTools: the session's tools (the CfL bit plays no part).
+template <int kTools>
+__device__ int intra_mode_wave(const Av1Args& A, int r, int c, int bsl, const ModeLds& S) {
+    const int mode = sad_mode_wave(A, r, c, bsl, S.E);
+    int ky = 0, kuv = 0;
+    if (r + (1 << bsl) > A.geo.mi_rows || c + (1 << bsl) > A.geo.mi_cols) return cand_pack(mode, 0, 0);
+    if (A.palette) {
+        int values;
+        ky = luma_palette_cand_wave(A, r, c, bsl, S, &values);
+        if (has_cluster(kTools) && values > kPalMax) ky = luma_cluster_cand_wave(A, r, c, bsl, S, values);
+        wsync();
+    }
+    if (has_uv(kTools)) {
+        kuv = chroma_palette_cand_wave(A, r, c, bsl, S.map);
+        wsync();
+    }
+    return cand_pack(mode, ky, kuv);
+}
+
+// The open-loop mode kernels, one wave per unit. Key frames (k_av1_intra_modes): every block; the
+// cell gets the mode, and the candidates' counts ride in it until k_av1_intra_rec decides. kTrial
+// (k_av1_cand_modes; inter frames with kToolIntraInter): every block whose inter coding kept levels
+// (k_av1_inter's cells: inter and not skipped); the cells stay the inter coding's, the word goes to A.cand.
+template <bool kTrial, int kTools>
+__device__ __forceinline__ void mode_units(const Av1Args& A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ IntraEdge E[4];
     __shared__ uint32_t pal_seen[4][8];
     __shared__ uint8_t pal_map[4][256], pal_col[4][8];
-    __shared__ uint32_t pal_hist[4][kCl ? 256 : 1];   // av1_palette_cluster: the luma histogram of the wave's block
-    if (A.frame[0]) return;
+    __shared__ uint32_t pal_hist[4][has_cluster(kTools) ? 256 : 1];
+    if ((A.frame[0] != 0) == kTrial) return;
     const FrameArgs& f = A.f;
     const Av1Geo& g = A.geo;
     const int w = threadIdx.x >> 6;
     const int u = blockIdx.x * 4 + w;
     if (u >= f.mb_w * f.mb_h) return;
+    const ModeLds S{E[w], pal_seen[w], pal_map[w], pal_col[w], pal_hist[w]};
     const int ux = u % f.mb_w, uy = u / f.mb_w;
     int nb = unit_blocks(g, uy, ux);
     const int bsl = nb < 0 ? 2 : 1;
     if (nb < 0) nb = 1;
     for (int k = 0; k < nb; k++) {
-        int r, c, pal_k;
+        int r, c;
         unit_block(g, uy, ux, k, r, c);
         const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
-        const BlkInfo b = A.blk[cell];
-        int cand = 0;
-        if (blk_inter(b) && !blk_skip(b)) {   // wave-uniform
-            const int mode = intra_mode_wave<kUv, kCl>(A, r, c, bsl, E[w], pal_seen[w], pal_map[w], pal_col[w], pal_hist[w], &pal_k);
-            cand = 1 | (mode << 8) | (pal_k << 16);
+        if (kTrial) {
+            const BlkInfo b = A.blk[cell];
+            const int cand = blk_inter(b) && !blk_skip(b) ? intra_mode_wave<kTools>(A, r, c, bsl, S) : 0;   // wave-uniform
+            if (lane() == 0) A.cand[cell] = cand;
+        } else {
+            const int cand = intra_mode_wave<kTools>(A, r, c, bsl, S);
+            BlkInfo b{};
+            b.bsl = (uint8_t)bsl;
+            b.mode = (uint8_t)cand_mode(cand);
+            b.uv_mode = DC_PRED;
+            b.pad1 = cand_pad1(cand);
+            set_cells(A, r, c, bsl, b);
         }
-        if (lane() == 0) A.cand[cell] = cand;
         wsync();
     }
 }
+template <int kTools>
+__global__ __launch_bounds__(256) void k_av1_intra_modes(Av1Args A) {
+    mode_units<false, kTools>(A);
+}
+template <int kTools>
+__global__ __launch_bounds__(256) void k_av1_cand_modes(Av1Args A) {
+    mode_units<true, kTools>(A);
+}
 
-// Reconstruction of one intra block by one wave. Key frames: mode and palette candidate from the
-// cells (cand = -1). kTrial (av1_intra_inter, inter frames): both from cand (k_av1_cand_modes);
-// the block is worked out in LDS and becomes the block's coding - reconstruction, levels, level
-// contexts, cells - only where its J plus the mode-bits bias is below the inter coding's
-// (av1_cpu.cpp intra_trial); otherwise nothing is stored.
-// kTools: the session's tools, bit 0 av1_chroma_palette (kUv), bit 1 av1_cfl (kCfl), bit 2
-// av1_palette_cluster (kCl).
+// Reconstruction of the intra block at (r, c) by one wave from its candidate word (mode and palette
+// candidates): the mode's coding (code_block_wave), then each candidate against the coding standing, in
+// the order and under the names of av1_cpu.cpp intra_code: try_luma_cluster or try_luma_palette,
+// try_chroma_palette, try_cfl. One body: split into functions, the steps made the compiler generate
+// longer code for code_block_wave (profiles/av1_tools.md). kTrial (inter frames): the block is worked
+// out in LDS and becomes the block's coding - reconstruction, levels, level contexts, cells - only where
+// its J plus the mode-bits bias is below the inter coding's (av1_cpu.cpp intra_trial); otherwise nothing
+// is stored. kTools: the session's tools.
 template <bool kTrial, int kTools>
 __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, int r, int c, int bsl, int qidx, int cand) {
     const FrameArgs& f = A.f;
@@ -853,14 +892,14 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     const TileRect t = tile_of(g, r, c);
     const bool au = inside(t, r - 1, c), al = inside(t, r, c - 1);
     const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
-    constexpr bool kUv = (kTools & 1) != 0, kCfl = (kTools & 2) != 0, kCl = (kTools & 4) != 0;
+    constexpr bool kUv = has_uv(kTools), kCfl = has_cfl(kTools), kCl = has_cluster(kTools);
     BlkInfo b{};
     if (kTrial) {
         b.bsl = (uint8_t)bsl;
-        b.mode = (uint8_t)(cand >> 8);
+        b.mode = (uint8_t)cand_mode(cand);
         b.uv_mode = DC_PRED;
-        b.pad1 = (uint8_t)((cand >> 16) & 255);
-    } else {
+        b.pad1 = cand_pad1(cand);
+    } else {   // key frames: the cell k_av1_intra_modes left is the same word (cand_of_cell)
         b = A.blk[cell];
     }
     IntraEdge* E = L.e;
@@ -875,8 +914,8 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     for (int i = l; i < n * n; i += 64)
         L.pred[i] = (uint8_t)(b.mode == DC_PRED ? dcy : intra_pred_px(E[0], b.mode, log2n, i / n, i % n));
     for (int i = l; i < cn * cn; i += 64) {
-        L.pred[256 + i] = (uint8_t)dcu;
-        L.pred[320 + i] = (uint8_t)dcv;
+        L.pred[kOffU + i] = (uint8_t)dcu;
+        L.pred[kOffV + i] = (uint8_t)dcv;
     }
     wsync();
     // levels in LDS until the decisions are made: a trial, or a session with chroma palettes or
@@ -886,23 +925,18 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
                                                  lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
     long long jreg = L.jreg;
     const uint32_t sdc = s;   // the UV_DC_PRED coding's summaries (the CfL gate)
-    b.tx_type = (int16_t)((s >> 25) & 1 ? TX_IDTX : TX_DCT_DCT);
-    // palette candidate from k_av1_intra_modes (colours already in the palette cells):
-    // exact palette of the source luma vs the transform path (av1_cpu.cpp intra_block)
-    const int kc = b.pad1 & 15, kuv = kUv ? b.pad1 >> 4 : 0;
+    b.tx_type = (int16_t)(summ_idtx(s) ? TX_IDTX : TX_DCT_DCT);
+    // luma palette candidate of the mode kernels (colours already in the palette cells)
+    const int kc = cand_ky(cand_of_cell(b)), kuv = kUv ? cand_kuv(cand_of_cell(b)) : 0;
     b.pad1 = 0;
     b.pal_n = 0;
     const bool clustered = kCl && kc && (A.pal_rate[cell] & kPalClusterMark);   // wave-uniform
     if (clustered) {
-        // clustered candidate (av1_palette_cluster; av1_cpu.cpp intra_code): every sample on its nearest
-        // colour, luma coded once more against that prediction. The coding standing waits in the chroma
-        // parts of L.b (256 levels) and L.lv2 (256 samples), both dead after code_block_wave.
+        // try_luma_cluster (av1_cpu.cpp): every sample on its nearest colour, luma coded once more against
+        // that prediction while the coding standing is parked
         const uint64_t C = pal_load8(A.pal + cell * 8);
-        int16_t* keep_lv = (int16_t*)(L.b + 256);
-        uint8_t* keep_rec = (uint8_t*)(L.lv2 + 256);
         for (int i = l; i < n * n; i += 64) {
-            keep_lv[i] = L.lv[i];
-            keep_rec[i] = L.pred[i];
+            park_luma(L, i);
             L.pred[i] = (uint8_t)pal_byte(C, palette_nearest(C, kc, L.src[i]));
         }
         wsync();
@@ -915,16 +949,13 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
             b.mode = DC_PRED;
             const uint32_t sy = recon_luma_wave(L, log2n, qidx, idtx);
             b.tx_type = (int16_t)(idtx ? TX_IDTX : TX_DCT_DCT);
-            s = (s & ~0xffu) | sy;
-            s = (s & ~(1u << 24)) | ((s & 0xffffffu) ? (1u << 24) : 0u);
+            s = summ_set_luma(s, sy);
         } else {
-            for (int i = l; i < n * n; i += 64) {
-                L.lv[i] = keep_lv[i];
-                L.pred[i] = keep_rec[i];
-            }
+            for (int i = l; i < n * n; i += 64) unpark_luma(L, i);
             wsync();
         }
     } else if (kc && tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx)) < jreg) {
+        // try_luma_palette: the exact palette of the source luma, no levels, vs the transform path
         jreg = tx_rd_cost(0, A.pal_rate[cell], ac_q(qidx));
         b.pal_n = (uint8_t)kc;
         b.mode = DC_PRED;
@@ -935,31 +966,27 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
             else gy[i] = 0;
             L.pred[i] = L.src[i];
         }
-        s &= ~0xffu;   // no luma levels: the summary and the skip flag come from chroma
-        s = (s & ~(1u << 24)) | ((s & 0xffff00u) ? (1u << 24) : 0u);
+        s = summ_clear_luma(s);   // the summary and the skip flag come from chroma
         wsync();
     }
-    // chroma palette candidate (av1_chroma_palette): the exact pairs of the source chroma vs both
-    // DCT planes (av1_cpu.cpp intra_code)
+    // try_chroma_palette: the exact pairs of the source chroma vs both DCT planes
     long long jchr = kTrial || kCfl ? L.jchr : 0;
     if (kUv && kuv && tx_rd_cost(0, A.pal_rate_uv[cell], ac_q(qidx)) < L.jchr) {   // kuv: levels in LDS
         jchr = tx_rd_cost(0, A.pal_rate_uv[cell], ac_q(qidx));
         b.pal_n = (uint8_t)(b.pal_n | (kuv << 4));
         for (int i = l; i < cn * cn; i += 64) {
-            L.lv[256 + i] = L.lv[320 + i] = 0;
-            L.pred[256 + i] = L.src[256 + i];
-            L.pred[320 + i] = L.src[320 + i];
+            L.lv[kOffU + i] = L.lv[kOffV + i] = 0;
+            L.pred[kOffU + i] = L.src[kOffU + i];
+            L.pred[kOffV + i] = L.src[kOffV + i];
         }
-        s &= ~0xffff00u;   // no chroma levels: the summary and the skip flag come from luma
-        s = (s & ~(1u << 24)) | ((s & 0xffu) ? (1u << 24) : 0u);
+        s = summ_clear_chroma(s);   // the summary and the skip flag come from luma
         wsync();
     }
-    // chroma from luma (av1_cfl; av1_cpu.cpp intra_code): a block whose UV_DC_PRED coding kept a
-    // chroma level and whose subsampled luma reconstruction varies. One chroma sample per lane
-    // (64 or 16 lanes); sums by wave reductions, every decision wave-uniform. The coding standing
-    // (levels, reconstruction) waits in the chroma half of L.lv2 and in L.a's luma part, both dead
-    // after code_block_wave, while both planes are coded again from the CfL prediction.
-    if (kCfl && (sdc & 0xffff00u)) {
+    // try_cfl: a block whose UV_DC_PRED coding kept a chroma level and whose subsampled luma
+    // reconstruction varies. One chroma sample per lane (64 or 16 lanes); sums by wave reductions,
+    // every decision wave-uniform. Both planes are coded again from the CfL prediction while the
+    // coding standing is parked.
+    if (kCfl && summ_chroma(sdc)) {
         const int cl2 = log2n - 1, cnn = cn * cn;
         const bool act = l < cnn;
         const int lum = act ? cfl_luma(L.pred, n, l >> cl2, l & (cn - 1)) : 0;
@@ -968,7 +995,7 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
         if (__ballot(ac != 0)) {
             const long long sxx = wsum(ac * ac);   // <= 64 x 2040^2 < 2^31
             const int dcu = intra_dc(E[1], cl2), dcv = intra_dc(E[2], cl2);
-            const int su = act ? L.src[256 + l] : 0, sv = act ? L.src[320 + l] : 0;
+            const int su = act ? L.src[kOffU + l] : 0, sv = act ? L.src[kOffV + l] : 0;
             int au = 0, av = 0;
             for (int p = 0; p < 2; p++) {
                 const int dc = p ? dcv : dcu, sp = p ? sv : su;
@@ -989,12 +1016,9 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
             }
             if (au || av) {
                 if (act) {
-                    L.lv2[256 + l] = L.lv[256 + l];
-                    L.lv2[320 + l] = L.lv[320 + l];
-                    L.a[l] = L.pred[256 + l];
-                    L.a[64 + l] = L.pred[320 + l];
-                    L.pred[256 + l] = (uint8_t)cfl_px(dcu, au, ac);
-                    L.pred[320 + l] = (uint8_t)cfl_px(dcv, av, ac);
+                    park_chroma(L, l);
+                    L.pred[kOffU + l] = (uint8_t)cfl_px(dcu, au, ac);
+                    L.pred[kOffV + l] = (uint8_t)cfl_px(dcv, av, ac);
                 }
                 wsync();
                 const long long jcfl = recode_chroma_wave(L, F, log2n, qidx) + tx_rd_cost(0, cfl_rate2(au, av), ac_q(qidx));
@@ -1004,15 +1028,9 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
                     b.pal_n &= 15;
                     b.mv_row = (int16_t)au;
                     b.mv_col = (int16_t)av;
-                    s = (s & ~0xffff00u) | recon_chroma_wave(L, log2n, qidx);
-                    s = (s & ~(1u << 24)) | ((s & 0xffffffu) ? (1u << 24) : 0u);
+                    s = summ_set_chroma(s, recon_chroma_wave(L, log2n, qidx));
                 } else {
-                    if (act) {
-                        L.lv[256 + l] = L.lv2[256 + l];
-                        L.lv[320 + l] = L.lv2[320 + l];
-                        L.pred[256 + l] = (uint8_t)L.a[l];
-                        L.pred[320 + l] = (uint8_t)L.a[64 + l];
-                    }
+                    if (act) unpark_chroma(L, l);
                     wsync();
                 }
             }
@@ -1025,33 +1043,42 @@ __device__ void intra_rec_block(const Av1Args& A, BlkLds& L, const FdctLds& F, i
     if (in_lds) {
         for (int p = 0; p < 3; p++) {
             int16_t* gp = lev_ptr(A, r, c, bsl, p);
-            const int m = p ? cn * cn : n * n, o = p == 0 ? 0 : (p == 1 ? 256 : 320);
+            const int m = p ? cn * cn : n * n, o = plane_off(p);
             for (int i = l; i < m; i += 64) gp[i] = L.lv[o + i];
         }
     }
     store_rec_blk(L, f, x, y, n);
-    b.flags = (s >> 24) & 1 ? 0 : 2;
+    b.flags = summ_any(s) ? 0 : 2;
     set_cells(A, r, c, bsl, b);
     const int n4 = 1 << bsl;
-    set_lctx(A, 0, c, r, n4, (uint8_t)(s & 0xff));
-    set_lctx(A, 1, c >> 1, r >> 1, n4 >> 1, (uint8_t)((s >> 8) & 0xff));
-    set_lctx(A, 2, c >> 1, r >> 1, n4 >> 1, (uint8_t)((s >> 16) & 0xff));
+    set_lctx(A, 0, c, r, n4, summ_plane(s, 0));
+    set_lctx(A, 1, c >> 1, r >> 1, n4 >> 1, summ_plane(s, 1));
+    set_lctx(A, 2, c >> 1, r >> 1, n4 >> 1, summ_plane(s, 2));
     wsync();
 }
 
-// Key frames: one workgroup (16 waves) per tile; unit (x, y) of the tile at step x + y.
-template <int kTools>
-__global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
+// The reconstruction wavefront of intra blocks: one workgroup (16 waves) per tile, unit (x, y) of the
+// tile at step x + y. Key frames (k_av1_intra_rec): every block, its candidate word from its cell.
+// kTrial (k_av1_inter_intra; inter frames with kToolIntraInter, after k_av1_inter and k_av1_cand_modes):
+// the blocks whose inter coding kept levels, tried as intra blocks in coding order. A candidate predicts
+// from its neighbours' reconstruction as it stands (an inter neighbour's is final, a candidate
+// neighbour's was decided at an earlier step). A tile without candidates returns before loading
+// anything; a unit without one costs its wave nothing but the step's barrier.
+template <bool kTrial, int kTools>
+__device__ __forceinline__ void intra_wavefront(const Av1Args& A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
     __shared__ BlkLds Lw[16];
     __shared__ FdctLds F;
-    if (!A.frame[0]) return;
+    if ((A.frame[0] != 0) == kTrial) return;
     const Av1Geo& g = A.geo;
     const int t = blockIdx.x;
+    if (kTrial && A.tile_cand[t] == 0) return;
     const TileRect tr = tile_rect(g, t);
     load_fdct(F);
     __syncthreads();
-    const int w = threadIdx.x >> 6;
+    // trial: the wave index as a scalar: the block position, its candidate word and the decision are
+    // wave-uniform and stay out of the vector registers the transforms need
+    const int w = kTrial ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
     const int ux0 = tr.mi_col0 >> 2, uy0 = tr.mi_row0 >> 2;
     const int uw = (tr.mi_col1 - tr.mi_col0 + 3) >> 2, uh = (tr.mi_row1 - tr.mi_row0 + 3) >> 2;
     const int qidx = A.frame[1];
@@ -1066,54 +1093,21 @@ __global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
             for (int k = 0; k < nb; k++) {
                 int r, c;
                 unit_block(g, uy0 + y, ux0 + x, k, r, c);
-                intra_rec_block<false, kTools>(A, Lw[w], F, r, c, bsl, qidx, -1);
+                const size_t cell = (size_t)(r >> 1) * g.c8 + (c >> 1);
+                const int cand = kTrial ? A.cand[cell] : cand_of_cell(A.blk[cell]);
+                if (cand_is(cand)) intra_rec_block<kTrial, kTools>(A, Lw[w], F, r, c, bsl, qidx, cand);
             }
         }
         __syncthreads();
     }
 }
-
-// Inter frames with av1_intra_inter, after k_av1_inter and k_av1_cand_modes: the blocks whose
-// inter coding kept levels, tried as intra blocks in coding order. One workgroup (16 waves) per
-// tile on k_av1_intra_rec's wavefront: a candidate predicts from its neighbours' reconstruction
-// as it stands (an inter neighbour's is final, a candidate neighbour's was decided at an earlier
-// step). A tile without candidates returns before loading anything; a unit without one costs
-// its wave nothing but the step's barrier.
+template <int kTools>
+__global__ __launch_bounds__(1024) void k_av1_intra_rec(Av1Args A) {
+    intra_wavefront<false, kTools>(A);
+}
 template <int kTools>
 __global__ __launch_bounds__(1024) void k_av1_inter_intra(Av1Args A) {
-    if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
-    __shared__ BlkLds Lw[16];
-    __shared__ FdctLds F;
-    if (A.frame[0]) return;
-    const Av1Geo& g = A.geo;
-    const int t = blockIdx.x;
-    if (A.tile_cand[t] == 0) return;
-    const TileRect tr = tile_rect(g, t);
-    load_fdct(F);
-    __syncthreads();
-    // the wave index as a scalar: the block position, its candidate word and the decision are
-    // wave-uniform and stay out of the vector registers the transforms need
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int ux0 = tr.mi_col0 >> 2, uy0 = tr.mi_row0 >> 2;
-    const int uw = (tr.mi_col1 - tr.mi_col0 + 3) >> 2, uh = (tr.mi_row1 - tr.mi_row0 + 3) >> 2;
-    const int qidx = A.frame[1];
-    const int steps = uw + uh - 1;
-    for (int s = 0; s < steps; s++) {
-        for (int y = w; y < uh; y += 16) {
-            const int x = s - y;
-            if (x < 0 || x >= uw) continue;
-            int nb = unit_blocks(g, uy0 + y, ux0 + x);
-            const int bsl = nb < 0 ? 2 : 1;
-            if (nb < 0) nb = 1;
-            for (int k = 0; k < nb; k++) {
-                int r, c;
-                unit_block(g, uy0 + y, ux0 + x, k, r, c);
-                const int cand = A.cand[(size_t)(r >> 1) * g.c8 + (c >> 1)];
-                if (cand & 1) intra_rec_block<true, kTools>(A, Lw[w], F, r, c, bsl, qidx, cand);
-            }
-        }
-        __syncthreads();
-    }
+    intra_wavefront<true, kTools>(A);
 }
 
 // Inter frames: one wave per unit, vector from the front end's motion search. kLtr: the
@@ -1158,29 +1152,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         // code_block_wave)
         uint8_t* win = reinterpret_cast<uint8_t*>(L.lv);
         mc_block(ref.y, f.stride_y, g.W - 1, g.H - 1, x, y, n, mv_row, mv_col, 0, n <= 4, win, L.a, L.pred);
-        mc_block(ref.u, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 256);
-        mc_block(ref.v, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + 320);
+        mc_block(ref.u, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + kOffU);
+        mc_block(ref.v, f.stride_c, lxc, lyc, x >> 1, y >> 1, cn, mv_row, mv_col, 1, cn <= 4, win, L.a, L.pred + kOffV);
         wsync();
         const uint32_t s = code_block_wave<kJ ? 1 : 0>(L, F, log2n, qidx, false, lev_ptr(A, r, c, bsl, 0),
                                                        lev_ptr(A, r, c, bsl, 1), lev_ptr(A, r, c, bsl, 2));
         if (kJ && l == 0) {
             A.jinter[(size_t)(r >> 1) * g.c8 + (c >> 1)] = L.jreg;
-            if ((s >> 24) & 1) atomicAdd(&A.tile_cand[((r >> 4) / g.tile_h_sb) * g.tile_cols + (c >> 4) / g.tile_w_sb], 1);
+            if (summ_any(s)) atomicAdd(&A.tile_cand[((r >> 4) / g.tile_h_sb) * g.tile_cols + (c >> 4) / g.tile_w_sb], 1);
         }
         store_rec_blk(L, f, x, y, n);
         BlkInfo b{};
         b.bsl = (uint8_t)bsl;
-        b.flags = (uint8_t)(1 | ((s >> 24) & 1 ? 0 : 2));
-        b.tx_type = (int16_t)((s >> 25) & 1 ? TX_IDTX : TX_DCT_DCT);
+        b.flags = (uint8_t)(1 | (summ_any(s) ? 0 : 2));
+        b.tx_type = (int16_t)(summ_idtx(s) ? TX_IDTX : TX_DCT_DCT);
         b.mv_row = (int16_t)mv_row;
         b.mv_col = (int16_t)mv_col;
         b.mode = GLOBALMV;
         b.pad1 = ref_last2;
         set_cells(A, r, c, bsl, b);
         const int n4 = 1 << bsl;
-        set_lctx(A, 0, c, r, n4, (uint8_t)(s & 0xff));
-        set_lctx(A, 1, c >> 1, r >> 1, n4 >> 1, (uint8_t)((s >> 8) & 0xff));
-        set_lctx(A, 2, c >> 1, r >> 1, n4 >> 1, (uint8_t)((s >> 16) & 0xff));
+        set_lctx(A, 0, c, r, n4, summ_plane(s, 0));
+        set_lctx(A, 1, c >> 1, r >> 1, n4 >> 1, summ_plane(s, 1));
+        set_lctx(A, 2, c >> 1, r >> 1, n4 >> 1, summ_plane(s, 2));
         wsync();
     }
 }
@@ -1565,8 +1559,8 @@ __device__ __forceinline__ void code_palette_tokens_uv(WaveTokenSink& w, const C
     wsync();
 }
 
-// kTools: bit 0, the session runs with av1_chroma_palette (code_unit's chroma palette syntax compiled
-// in); bit 1, with av1_cfl (the CfL alphas' syntax); bit 2, with av1_palette_cluster (luma index maps by nearest colour).
+// kTools (av1_core.h Tools): the syntax code_unit compiles in - chroma palettes, CfL alphas, luma index
+// maps by nearest colour.
 template <int kTools>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_av1_tokens(Av1Args A) {
     if (second_pass_skipped(A.f)) return;   // K10: no re-code this frame
@@ -1589,7 +1583,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     v.unit_w = f.mb_w;
     v.qidx = A.frame[1];
     v.key = A.frame[0];
-    v.screen = (A.frame[0] || A.intra_inter) && A.palette;
+    v.screen = frame_screen(A.frame[0] != 0, A.tools, A.palette != 0);
     v.pal = A.pal;
     v.src_y = f.src.y;
     v.stride_y = f.stride_y;
@@ -1600,7 +1594,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     const int ux = u % f.mb_w, uy = u / f.mb_w;
     WaveTokenSink sink{A.tok + (size_t)u * kTokCap, 0, kTokCap, 0u, 0, bits_w[w]};
     const TileRect t = tile_of(g, uy * 4, ux * 4);
-    code_unit<WaveTokenSink, (kTools & 1) != 0, (kTools & 2) != 0, (kTools & 4) != 0>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
+    code_unit<WaveTokenSink, has_uv(kTools), has_cfl(kTools), has_cluster(kTools)>(sink, AV1_DEFAULT_CDF[0], v, t, ux, uy);
     sink.flush();
     if (lane() == 0) A.tok_n[u] = sink.n;
 }
@@ -2272,64 +2266,45 @@ void ec_buffers(int tiles, int tile_bytes, int* max_blocks, int* vcap) {
     *vcap = tile_bytes / 4 + 8;
 }
 
-// The kernels that depend on the session's tools (kTools: bit 0 av1_chroma_palette, bit 1 av1_cfl,
-// bit 2 av1_palette_cluster): the ones with the candidate, decision and syntax in place of the ones
-// without, the same launches either way. The open-loop mode kernels know the two palette tools only.
-template <int kTools>
-static void launch_intra(const Av1Args& a, int n, int tiles, hipStream_t s) {
-    hipLaunchKernelGGL((k_av1_intra_modes<(kTools & 1) != 0, (kTools & 4) != 0>), dim3((n + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_av1_intra_rec<kTools>, dim3(tiles), dim3(1024), 0, s, a);
-}
-template <int kTools>
-static void launch_inter_intra(const Av1Args& a, int n, int tiles, hipStream_t s) {
-    hipLaunchKernelGGL((k_av1_cand_modes<(kTools & 1) != 0, (kTools & 4) != 0>), dim3((n + 3) / 4), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_av1_inter_intra<kTools>, dim3(tiles), dim3(1024), 0, s, a);
-}
-template <int kTools>
-static void launch_tokens(const Av1Args& a, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_av1_tokens<kTools>, dim3((n + 3) / 4), dim3(256), 0, s, a);
-}
-#define SK_BY_TOOLS(tools, call)            \
-    switch (tools) {                        \
-        case 0: call(0); break;             \
-        case 1: call(1); break;             \
-        case 2: call(2); break;             \
-        case 3: call(3); break;             \
-        case 4: call(4); break;             \
-        case 5: call(5); break;             \
-        case 6: call(6); break;             \
-        default: call(7); break;            \
+// fn(std::integral_constant<int, K>) for K = the kernel bits of the session's tools: the launches of
+// the kernels that are instantiated per tools word.
+template <int K = 0, class Fn>
+static void by_tools(int tools, Fn&& fn) {
+    if constexpr (K <= kToolsKernel) {
+        if ((tools & kToolsKernel) == K) fn(std::integral_constant<int, K>{});
+        else by_tools<K + 1>(tools, fn);
     }
+}
 
 // Block decisions, reconstruction and the arithmetic-coded tiles: everything the coded
-// size depends on (the K10 guard re-runs it, gated).
+// size depends on (the K10 guard re-runs it, gated). The same launches whatever the tools.
 static void launch_code(const Av1Args& a, hipStream_t s) {
     const int n = a.f.mb_w * a.f.mb_h;
     const int tiles = a.geo.tile_cols * a.geo.tile_rows;
+    const dim3 units((n + 3) / 4);   // one wave per unit, four to a workgroup
     hipLaunchKernelGGL(k_av1_setup, dim3(1), dim3(256), 0, s, a);
-    const int tools = (a.chroma_palette ? 1 : 0) | (a.cfl ? 2 : 0) | (a.palette_cluster ? 4 : 0);
-#define SK_INTRA(k) launch_intra<k>(a, n, tiles, s)
-    SK_BY_TOOLS(tools, SK_INTRA)
-#undef SK_INTRA
+    by_tools(a.tools, [&](auto k) {   // the open-loop mode kernels know the two palette tools only
+        hipLaunchKernelGGL(k_av1_intra_modes<(k() & ~kToolCfl)>, units, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_av1_intra_rec<k()>, dim3(tiles), dim3(1024), 0, s, a);
+    });
     const bool ltr_on = a.f.ltr_cfg.mode == ltr::LTR_BUFMAP;
-    if (a.intra_inter) {   // av1_intra_inter: the inter coding with its J, then the candidates as intra blocks
-        if (ltr_on) hipLaunchKernelGGL((k_av1_inter<true, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_av1_inter<false, true>), dim3((n + 3) / 4), dim3(256), 0, s, a);
-#define SK_INTER_INTRA(k) launch_inter_intra<k>(a, n, tiles, s)
-        SK_BY_TOOLS(tools, SK_INTER_INTRA)
-#undef SK_INTER_INTRA
+    if (has_intra_inter(a.tools)) {   // the inter coding with its J, then the candidates as intra blocks
+        if (ltr_on) hipLaunchKernelGGL((k_av1_inter<true, true>), units, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_av1_inter<false, true>), units, dim3(256), 0, s, a);
+        by_tools(a.tools, [&](auto k) {
+            hipLaunchKernelGGL(k_av1_cand_modes<(k() & ~kToolCfl)>, units, dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_av1_inter_intra<k()>, dim3(tiles), dim3(1024), 0, s, a);
+        });
     } else if (ltr_on) {
-        hipLaunchKernelGGL((k_av1_inter<true, false>), dim3((n + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_av1_inter<true, false>), units, dim3(256), 0, s, a);
     } else {
-        hipLaunchKernelGGL((k_av1_inter<false, false>), dim3((n + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_av1_inter<false, false>), units, dim3(256), 0, s, a);
     }
     hipLaunchKernelGGL(k_av1_merge, dim3(a.geo.sb_cols * a.geo.sb_rows), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_av1_modes, dim3((a.geo.c8 * a.geo.r8 + 255) / 256), dim3(256), 0, s, a);
-#define SK_TOKENS(k) launch_tokens<k>(a, n, s)
-    SK_BY_TOOLS(tools, SK_TOKENS)
-#undef SK_TOKENS
+    by_tools(a.tools, [&](auto k) { hipLaunchKernelGGL(k_av1_tokens<k()>, units, dim3(256), 0, s, a); });
     hipLaunchKernelGGL(k_av1_tok_scan, dim3(tiles), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_av1_tok_copy, dim3((n + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_av1_tok_copy, units, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_av1_cdf, dim3(tiles * kEcParts), dim3(64), 0, s, a);
     launch_ec(a, tiles, s);
 }

@@ -35,13 +35,10 @@ struct Av1Tail {
         a.pal = mem.dmalloc<uint8_t>((size_t)geo_.c8 * geo_.r8 * 8);
         a.palette = av1::palette_enabled() ? 1 : 0;
         a.pal_rate = mem.dmalloc<int>((size_t)geo_.c8 * geo_.r8);
-        a.chroma_palette = cfg.av1_chroma_palette > 0 && a.palette;
+        a.tools = av1::session_tools(cfg, a.palette != 0);
         a.pal_uv = mem.dmalloc<uint8_t>((size_t)geo_.c8 * geo_.r8 * 16);
         a.pal_rate_uv = mem.dmalloc<int>((size_t)geo_.c8 * geo_.r8);
-        a.cfl = cfg.av1_cfl > 0;
-        a.palette_cluster = cfg.av1_palette_cluster > 0 && a.palette;
-        a.intra_inter = cfg.av1_intra_inter > 0;
-        if (a.intra_inter) {   // av1_gpu.h: the inter coding's J, the intra candidates and their count per tile
+        if (av1::has_intra_inter(a.tools)) {   // av1_gpu.h: the inter coding's J, the intra candidates and their count per tile
             a.jinter = mem.dmalloc<long long>((size_t)geo_.c8 * geo_.r8);
             a.cand = mem.dmalloc<int>((size_t)geo_.c8 * geo_.r8);
             a.tile_cand = mem.dmalloc<int>((size_t)geo_.tile_cols * geo_.tile_rows);
@@ -120,7 +117,7 @@ struct Av1Tail {
             fp.last_buf = o.frame.host[4];
             fp.last2_buf = o.frame.host[5];
         }
-        fp.screen = (fp.key || aargs_.intra_inter) && aargs_.palette;
+        fp.screen = av1::frame_screen(fp.key != 0, aargs_.tools, aargs_.palette != 0);
         std::vector<std::vector<uint8_t>> tl(tiles);
         size_t off = 0;
         for (int t = 0; t < tiles; t++) {
@@ -129,31 +126,11 @@ struct Av1Tail {
             tl[t].assign(o.data.host + off, o.data.host + off + n);
             off += (size_t)n;
         }
-        size_t maxsz = 1;
-        for (int t = 0; t + 1 < tiles; t++) maxsz = std::max(maxsz, tl[t].size());
-        fp.tile_size_bytes = maxsz <= 0x100 ? 1 : (maxsz <= 0x10000 ? 2 : (maxsz <= 0x1000000 ? 3 : 4));
         EncodedPacket pk;
         pk.y = 0; pk.w = g.W; pk.h = g.H; pk.key = fp.key;
         pk.data.resize(10);
         write_stripe_header(pk.data.data(), fp.key, f.frame, 0, g.W, g.H);
-        av1::append_obu(pk.data, 2, nullptr, 0);
-        if (fp.key) {
-            av1::BitWriter sh;
-            av1::write_sequence_header(sh, g.W, g.H, level_, s_.cfg.full_range);
-            av1::append_obu(pk.data, 1, sh.buf.data(), sh.buf.size());
-        }
-        av1::BitWriter fh;
-        av1::write_frame_header(fh, geo_, fp);
-        std::vector<uint8_t> payload = fh.buf;
-        if (tiles > 1) payload.push_back(0);
-        for (int t = 0; t < tiles; t++) {
-            if (t + 1 < tiles) {
-                const uint32_t sz = (uint32_t)tl[t].size() - 1;
-                for (int k = 0; k < fp.tile_size_bytes; k++) payload.push_back((uint8_t)(sz >> (8 * k)));
-            }
-            payload.insert(payload.end(), tl[t].begin(), tl[t].end());
-        }
-        av1::append_obu(pk.data, 6, payload.data(), payload.size());
+        av1::write_temporal_unit(pk.data, geo_, fp, tl, level_, s_.cfg.full_range);
         out.push_back(std::move(pk));
     }
 

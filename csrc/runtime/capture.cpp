@@ -122,10 +122,7 @@ class CaptureSession {
                     e.intra4x4 = 0;
                     e.deblock = 0;   // their own in-loop filters, not the H.264 front end's
                 }
-                e.av1_intra_inter = e.codec == 2 && s.av1_intra_inter > 0 ? 1 : 0;
-                e.av1_chroma_palette = e.codec == 2 && s.av1_chroma_palette > 0 ? 1 : 0;
-                e.av1_cfl = e.codec == 2 && s.av1_cfl > 0 ? 1 : 0;
-                e.av1_palette_cluster = e.codec == 2 && s.av1_palette_cluster > 0 ? 1 : 0;
+                h264::set_av1_tools(e, s.av1_intra_inter, s.av1_chroma_palette, s.av1_cfl, s.av1_palette_cluster);
                 if (const char* err = h264::ltr_config_error(e)) throw std::runtime_error(err);
                 ecfg_ = e;
                 enc_.reset(backend ? create_hip_backend(e, s.device) : create_cpu_backend(e));

@@ -234,10 +234,7 @@ h264::EncoderConfig to_config(const sk_h264_config* c) {
     e.subpel = c->subpel >= 0 ? 1 : 0;
     e.intra4x4 = c->intra4x4 > 0 ? 1 : 0;
     e.ltr_slots = c->ltr_slots > 0 ? c->ltr_slots : 0;
-    e.av1_intra_inter = c->codec == 2 && c->av1_intra_inter > 0 ? 1 : 0;
-    e.av1_chroma_palette = c->codec == 2 && c->av1_chroma_palette > 0 ? 1 : 0;
-    e.av1_cfl = c->codec == 2 && c->av1_cfl > 0 ? 1 : 0;
-    e.av1_palette_cluster = c->codec == 2 && c->av1_palette_cluster > 0 ? 1 : 0;
+    h264::set_av1_tools(e, c->av1_intra_inter, c->av1_chroma_palette, c->av1_cfl, c->av1_palette_cluster);
     if (e.codec >= 1) {   // HEVC / AV1: full-frame pictures, slices of whole CTB rows, one reference
         e.aq_strength = 0;   // no cu_qp_delta in this HEVC profile setup
         e.fullframe = 1;

@@ -317,6 +317,8 @@ LTR_TASK_DTYPE = np.dtype([("slot", "<i4"), ("store_slot", "<i4"), ("mmco1", "<i
 
 
 RC_MODES = {"cqp": 0, "crf": 1, "cbr": 2}
+# the AV1 tools' keywords of the encoder constructors, in the order of the C structs' fields
+AV1_TOOL_KWARGS = ("av1_intra_inter", "av1_chroma_palette", "av1_cfl", "av1_palette_cluster")
 RC_FIELDS = ("mode", "base_qp", "qp_min", "qp_max", "budget", "vbv_size", "fullness", "frames", "last_qp_p",
              "last_qp_i", "last_bits_p", "last_bits_i", "last_cplx_p", "last_cplx_i", "cplx_ema", "cur_qp",
              "cur_intra", "cur_cplx", "max_p_bits", "seq", "cur_valid", "pixels", "cur_idr", "redos", "qp_floor", "floor_age", "last_mbs_p", "last_mbs_i", "cur_mbs", "vbv_ms", "last_qpf_p", "last_qpf_i", "cur_qpf",
@@ -356,6 +358,7 @@ class H264Encoder:
             raise ValueError("backend must be 'cpu' or 'hip'")
         if backend == "hip":
             require_gpu()
+        given = locals()   # the AV1 tools' keywords by name
         self.cfg = SkH264Config(width, height, stripe_height, int(fullframe), int(full_range), qp, paint_qp,
                                 int(use_paint_over), paint_over_trigger, paint_over_burst, int(streaming_mode),
                                 damage_threshold, damage_duration, me_range, me_iters, int(scenecut), fps,
@@ -365,10 +368,7 @@ class H264Encoder:
                                 int(round(aq_strength * 16)), 0 if subpel else -1, 1 if intra4x4 else 0,
                                 int(tile_cols_log2), int(tile_rows_log2),
                                 RC_MODES[rate_control], int(bitrate_kbps), int(ltr_slots),
-                                1 if av1_intra_inter and codec == "av1" else 0,
-                                1 if av1_chroma_palette and codec == "av1" else 0,
-                                1 if av1_cfl and codec == "av1" else 0,
-                                1 if av1_palette_cluster and codec == "av1" else 0)
+                                *(1 if given[name] and codec == "av1" else 0 for name in AV1_TOOL_KWARGS))
         if codec not in ("h264", "hevc", "av1"):
             raise ValueError("codec must be 'h264', 'hevc' or 'av1'")
         self.codec = codec
@@ -664,13 +664,8 @@ class Av1Encoder(H264Encoder):
     def __init__(self, width: int, height: int, *, intra_inter: bool = False, chroma_palette: bool = False,
                  cfl: bool = False, palette_cluster: bool = False, **kw):
         kw.pop("fullframe", None)
-        kw.pop("av1_intra_inter", None)
-        kw.pop("av1_chroma_palette", None)
-        kw.pop("av1_cfl", None)
-        kw.pop("av1_palette_cluster", None)
-        super().__init__(width, height, codec="av1", fullframe=True, av1_intra_inter=bool(intra_inter),
-                         av1_chroma_palette=bool(chroma_palette), av1_cfl=bool(cfl),
-                         av1_palette_cluster=bool(palette_cluster), **kw)
+        kw.update(zip(AV1_TOOL_KWARGS, map(bool, (intra_inter, chroma_palette, cfl, palette_cluster))))
+        super().__init__(width, height, codec="av1", fullframe=True, **kw)
 
 
 class JpegEncoder(H264Encoder):

@@ -193,28 +193,30 @@ def _ltr_slots_from_env(name: str = "SELKIES_H264_LTR_SLOTS") -> int:
         return 0
 
 
+def _env_flag(name: str) -> int:
+    """1 where the environment variable `name` is 1 / true / yes / on, else 0."""
+    return int(os.environ.get(name, "").strip().lower() in ("1", "true", "yes", "on"))
+
+
+# The tools of AV1 (svtav1enc) sessions (csrc/codec/av1_core.h), each default off:
 def _av1_intra_inter_from_env() -> int:
-    """SELKIES_AV1_INTRA_INTER: intra blocks and luma palettes in the inter frames of AV1 (svtav1enc)
-    sessions (csrc/codec/av1_core.h), 1 / true / yes / on = on, default off."""
-    return int(os.environ.get("SELKIES_AV1_INTRA_INTER", "").strip().lower() in ("1", "true", "yes", "on"))
+    """SELKIES_AV1_INTRA_INTER: intra blocks and luma palettes in the inter frames."""
+    return _env_flag("SELKIES_AV1_INTRA_INTER")
 
 
 def _av1_chroma_palette_from_env() -> int:
-    """SELKIES_AV1_CHROMA_PALETTE: exact chroma palettes on the intra blocks of AV1 (svtav1enc)
-    sessions (csrc/codec/av1_core.h), 1 / true / yes / on = on, default off."""
-    return int(os.environ.get("SELKIES_AV1_CHROMA_PALETTE", "").strip().lower() in ("1", "true", "yes", "on"))
+    """SELKIES_AV1_CHROMA_PALETTE: exact chroma palettes on the intra blocks."""
+    return _env_flag("SELKIES_AV1_CHROMA_PALETTE")
 
 
 def _av1_cfl_from_env() -> int:
-    """SELKIES_AV1_CFL: chroma from luma on the intra blocks of AV1 (svtav1enc) sessions
-    (csrc/codec/av1_core.h), 1 / true / yes / on = on, default off."""
-    return int(os.environ.get("SELKIES_AV1_CFL", "").strip().lower() in ("1", "true", "yes", "on"))
+    """SELKIES_AV1_CFL: chroma from luma on the intra blocks."""
+    return _env_flag("SELKIES_AV1_CFL")
 
 
 def _av1_palette_cluster_from_env() -> int:
-    """SELKIES_AV1_PALETTE_CLUSTER: clustered luma palettes with a residual on the intra blocks of AV1
-    (svtav1enc) sessions (csrc/codec/av1_core.h), 1 / true / yes / on = on, default off."""
-    return int(os.environ.get("SELKIES_AV1_PALETTE_CLUSTER", "").strip().lower() in ("1", "true", "yes", "on"))
+    """SELKIES_AV1_PALETTE_CLUSTER: clustered luma palettes with a residual on the intra blocks."""
+    return _env_flag("SELKIES_AV1_PALETTE_CLUSTER")
 
 
 def files_listing_html(path: str, rel: str) -> str:
