@@ -77,6 +77,7 @@ DebugBuf codec_debug(hevc::CpuHevcEncoder& e, const std::string& s) {
     if (s == "sao") return bytes_of(e.sao);
     if (s == "coefs") return bytes_of(e.coefs);
     if (s == "bin_n") return bytes_of(e.bin_n);
+    if (s == "bins") return bytes_of(e.bins);   // the binariser's entries (hevc_core.h BinBuf): context indices, not states
     if (s == "pc_dbg") return bytes_of(e.pc_dbg_);
     if (s.compare(0, 3, "ltr") == 0) return ltr_debug(e.fe, s);
     return {nullptr, -1};

@@ -138,6 +138,7 @@ def snapshot(enc, r, packets):
         s["blk"] = enc.debug_buffer("blk").reshape(-1, BLK).copy()
         s["levels"] = enc.debug_buffer("levels", np.int16).copy()
         s["av1_qidx"] = int(enc.debug_buffer("av1_qidx", np.int32)[0])
+        s["src_y"] = enc.debug_buffer("src_y").reshape(-1, (W + 15) // 16 * 16)[:H, :W].copy()
     else:   # H.264: the buffers tests/test_h264_gpu.py _compare_state reads
         s["state"] = {n: enc.debug_buffer(n).copy() for n in H264_STATE}
     return s

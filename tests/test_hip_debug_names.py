@@ -17,7 +17,8 @@ ENCODERS = dict(h264=H264Encoder, hevc=HevcEncoder, av1=Av1Encoder)
 FRONT = ("src_y", "src_u", "src_v", "ref_y", "ref_u", "ref_v", "me", "tasks", "ltr_state", "ltr_task", "ltr0_y")
 # codec_debug of the CPU back end (sk_api.cpp) without the cache's names, which are in FRONT, and
 # without HEVC's "pc_dbg": the CPU encoder's own trace of its parallel CABAC pass, which the HIP back
-# end never had (HIP_ONLY below holds its counterparts)
+# end never had (HIP_ONLY below holds its counterparts), and without HEVC's "bins": the binariser's
+# entries with their context indices, which k_pc_model replaces by modelled states on the device
 CODEC = dict(h264=("ref1_y", "mbs", "coefs", "mb_dirty", "aq", "fs_mv"),
              hevc=("cus", "sao", "coefs", "bin_n"),
              av1=("blk", "levels", "av1_geo", "av1_qidx"))
